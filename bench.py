@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched AquaEnv step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no launcher around it starts the second form itself, as a fresh child process,
@@ -14,18 +14,23 @@ obstacles, waves on, Philox noise, auto-reset on.  N > 1: the same batch PER GPU
 range-partitioned global world indices, the done mask exchanged on side streams (peer copies through hipIpcMemHandle
 when the ranks can map each other's buffers, else RCCL's all-gather).
 
-Protocol: W untimed warm-up steps, then timed regions (max(5, ceil(2000 / K)) of them) of EXACTLY K
-steps each, every region bracketed by barrier + torch.cuda.synchronize() on both sides (a rank's clock
-stops when ITS queue has drained, steps and done-mask gathers; the barrier follows) and reduced
-with MAX over the ranks; the MEDIAN region is the one reported (`value`, `ms_per_step`; all of them are
-listed under `regions_ms`, the first five are also reported on their own: `roofline.first_regions`).  Steps are queued as replays of captured HIP graphs of min(CHUNK, K) steps
-(+ one graph for the remainder), so that any K >= 1 and W >= 0 runs the same way.  Inputs are resident
-in HBM before the timed regions.  `roofline` comes from HIP events recorded on the launch stream around each region's
-launches.  Rank 0 prints ONE JSON line.
+Protocol: W untimed warm-up steps, then EXACTLY K timed steps, split into timed regions
+(min(5, K) of them, as equal as they can be: `region_steps`), every region bracketed by barrier + torch.cuda.synchronize()
+on both sides (a rank's clock stops when ITS queue has drained, steps and done-mask gathers; the barrier follows) and
+reduced with MAX over the ranks; the region with the MEDIAN time per step is the one reported (`value`, `ms_per_step`; all
+of them are listed under `regions_ms`, the first five are also reported on their own: `roofline.first_regions`).  Steps are
+queued as replays of captured HIP graphs of min(CHUNK, region) steps (+ one graph for the remainder), so that any K >= 1
+and W >= 0 runs the same way.  Inputs are resident in HBM before the timed regions.  `roofline` comes from HIP events
+recorded on the launch stream around each region's launches.  Rank 0 prints ONE JSON line.
 
-The CPU baselines (`cpu_baseline*`, oracle/ = test infrastructure, never the product path) run BEFORE
-the process touches the GPU: their worker processes are started with fork+exec, which must not happen
-from a process that has initialised HIP.
+A plain run does only that.  --full adds what takes runs of its own: the CPU baselines (`cpu_baseline*`), the fused
+rollout kernel (`extras.fused_rollout`) and per-world obstacle tables (`extras.per_world_tables`).  The CPU baselines
+(oracle/ = test infrastructure, never the product path) run BEFORE the process touches the GPU: their worker processes are
+started with fork+exec, which must not happen from a process that has initialised HIP.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path left for its caller after its last step
+(DUMPED_ARRAYS, float32, one .npy each; a fixed sample of the worlds when they would exceed DUMP_LIMIT_BYTES).  The inputs
+depend on the arguments only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -44,18 +49,20 @@ HBM_PEAK_GBPS = 8000.0
 HBM_COPY_GBPS = 6290.0   # measured float4 copy (MI355X_MICROARCH.md chip table): SURVEY.md 8(d) asks for this fraction too
 CHUNK = 100          # steps per captured HIP graph (at most)
 GATHER_EVERY = 5     # chunks per done-mask block: one [GATHER_EVERY * CHUNK][words] all-gather per block (N > 1)
-REGIONS = 5          # timed regions at least; the median is reported
-MIN_TIMED_STEPS = 2000   # ... and at least this many timed steps in all (one default region's worth): see regions_for()
+REGIONS = 5          # timed regions the K timed steps are split into (fewer when K < 5); the median is reported
+MIN_TIMED_STEPS = 2000   # regions_for(): the default region count of the extra legs of an N > 1 run
 MAX_REGIONS = 400
 ROLLBACK_BELOW_REGIONS = 20   # the untimed, rolled-back first replay of the timed graphs is made only for fewer regions than this
 AB_MIN_REGIONS = 20      # N > 1: regions of every extra leg (the other transport, the step path alone)
 OUTLIER_FACTOR = 1.5     # regions_outliers: regions slower than this x the median
+DUMPED_ARRAYS = ("obs", "wave", "reward", "term", "time")     # --dump-outputs: DIR/<name>.npy
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps in all (split into --regions regions)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--envs", type=int, default=262144, help="worlds per GPU")
     ap.add_argument("--continuous", action="store_true", help="configs[3]: continuous actions")
@@ -63,11 +70,16 @@ def parse(argv=None):
     ap.add_argument("--no-auto-reset", action="store_true", help="diagnostic only: finished worlds are not restarted")
     ap.add_argument("--reset-mode", type=int, default=2, choices=(1, 2),
                     help="restart of finished worlds: 2 = during the next step (default, fastest), 1 = inside the same launch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: the CPU baselines (unless --no-cpu-baseline), "
+                         "--extras and --per-world-tables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of EACH CPU baseline leg")
     ap.add_argument("--regions", type=int, default=None,
-                    help="timed regions of --steps steps each (median reported); default: max(%d, ceil(%d / steps)), see regions_for()"
-                         % (REGIONS, MIN_TIMED_STEPS))
+                    help="timed regions the --steps timed steps are split into (median reported); default: min(%d, steps)"
+                         % REGIONS)
     ap.add_argument("--eager", action="store_true", help="no HIP graph: one C-side launch loop per chunk")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the done-mask exchange (side streams) even on one GPU: rehearsal of the N > 1 path")
@@ -107,7 +119,7 @@ def parse(argv=None):
                          "is queued by one C call of plain launches, its events ATTACHED to the first launch (start time) and the "
                          "last one (end time) by hipExtLaunchKernel; the stream events are recorded as well and reported beside "
                          "them.  Measured on one box at --steps 20 (profiles/r03/region_clock.txt): 5.1-5.4 us per step by the "
-                         "attached events against 5.5 by the stream events around a graph -- and 13-17 %% less throughput by wall "
+                         "attached events against 5.5 by the stream events around a graph -- and 13-17 percent less throughput by wall "
                          "clock, noisier regions (the host queues every launch): not the default" % CHUNK)
     ap.add_argument("--first-replay", choices=("upload", "rollback"), default="rollback",
                     help="graphs of the timed region that the warm-up budget cannot replay (warmup < steps): 'upload' = "
@@ -124,7 +136,8 @@ def parse(argv=None):
                     help="N > 1 (or --force-exchange): skip the extra legs behind the main regions (extras.exchange_ab: the "
                          "step path alone, and the transport the main regions did NOT use)")
     ap.add_argument("--ab-regions", type=int, default=None,
-                    help="regions of each extra leg; default: max(%d, the main regions' rule)" % AB_MIN_REGIONS)
+                    help="regions of each extra leg, as long as the longest main region; default: max(%d, regions_for(that "
+                         "length))" % AB_MIN_REGIONS)
     ap.add_argument("--ab-deadline", type=float, default=120.0,
                     help="seconds all extra legs together may take: past it rank 0 prints the line with what it has and "
                          "extras.exchange_ab.error naming the stage, and every rank exits with status 0 (the main line is "
@@ -141,26 +154,33 @@ def parse(argv=None):
     if args.warmup < 0:
         ap.error("--warmup must be >= 0")
     if args.regions is None:
-        args.regions, args.regions_rule = regions_for(args.steps), "max(%d, ceil(%d / steps))" % (REGIONS, MIN_TIMED_STEPS)
+        args.regions, args.regions_rule = min(REGIONS, args.steps), "min(%d, steps)" % REGIONS
     else:
         args.regions_rule = "--regions"
-    if args.regions < 1:
-        ap.error("--regions must be >= 1")
+    if not 1 <= args.regions <= args.steps:
+        ap.error("--regions must be >= 1 and <= --steps")
+    args.region_steps = split_steps(args.steps, args.regions)
     if args.ab_regions is None:
-        args.ab_regions = max(AB_MIN_REGIONS, regions_for(args.steps))
+        args.ab_regions = max(AB_MIN_REGIONS, regions_for(args.region_steps[0]))     # the legs' regions are this long
     if args.ab_regions < 1:
         ap.error("--ab-regions must be >= 1")
     return args
 
 
 def regions_for(steps):
-    """How many timed regions of `steps` steps: five at least, and as many as it takes to time MIN_TIMED_STEPS steps in all.
-    Five regions of 20 steps are 0.6 ms of GPU work on a GPU that has been busy for less than a millisecond since the process
-    started: they read 0.3-0.5 us per step above what the same command reads a few milliseconds later (60 regions: the first 14
-    at 5.1-5.5 us, the rest at 4.7-5.1: profiles/FLOOR.md) -- a sample too short for the median to mean anything.  Every
-    region is still exactly `steps` steps between its own brackets and is listed; the first five are also reported on their
-    own (roofline.first_regions)."""
+    """How many regions of `steps` steps an extra leg of an N > 1 run times by default: five at least, and as many as it
+    takes to time MIN_TIMED_STEPS steps in all.  Five regions of 20 steps are 0.6 ms of GPU work on a GPU that has been busy
+    for less than a millisecond since the process started: they read 0.3-0.5 us per step above what the same command reads a
+    few milliseconds later (60 regions: the first 14 at 5.1-5.5 us, the rest at 4.7-5.1: profiles/FLOOR.md) -- a sample too
+    short for the median to mean anything."""
     return min(MAX_REGIONS, max(REGIONS, -(-MIN_TIMED_STEPS // max(steps, 1))))
+
+
+def split_steps(steps, regions):
+    """the lengths of `regions` timed regions that hold exactly `steps` steps in all: as equal as they can be, the longer
+    ones first (at most two lengths, so at most two sets of graphs)"""
+    q, r = divmod(steps, regions)
+    return [q + 1] * r + [q] * (regions - r)
 
 
 # ------------------------------------------------------------------ the step queue (host logic; tests/test_bench_logic.py)
@@ -385,7 +405,7 @@ def summarize_regions(walls_s, events_ms, steps, n, world, a_bytes):
 
 
 class RegionClock(object):
-    """Times sets of regions of `steps` steps on this rank.  A region: opening bracket = the closing bracket of what ran
+    """Times sets of regions of `steps` steps (or of the given lengths) on this rank.  A region: opening bracket = the closing bracket of what ran
     before it (barrier + synchronize); the clock starts; the runner queues the steps (HIP events recorded on `stream` right
     around its launches); drain() -- this rank's queue is empty, steps and done-mask copies; the clock stops; rendezvous().
     Without a device (torch None: the CPU tests) the wall clock stands in for the events."""
@@ -414,12 +434,15 @@ class RegionClock(object):
         if exchange is not None:
             exchange.note_fence()
 
-    def run(self, n_regions, exchange):
-        """-> (wall seconds per region, event milliseconds per region, the last region's segments); call between two
-        rendezvous() (it ends with one)"""
+    def run(self, n_regions, exchange, lengths=None):
+        """-> (wall seconds per region, event milliseconds per region, the last region's segments); region i has lengths[i]
+        steps (default: self.steps each); call between two rendezvous() (it ends with one)"""
         walls, events, segs = [], [], []
         torch, stream = self.torch, self.stream
-        for _ in range(n_regions):
+        lengths = [self.steps] * n_regions if lengths is None else lengths
+        if len(lengths) != n_regions:
+            raise ValueError("%d region lengths for %d regions" % (len(lengths), n_regions))
+        for steps in lengths:
             if torch is not None:
                 # HIP events on the stream the step kernels are launched on, around the region's launches (the contract's
                 # `roofline` clock).  Round 2 timed a one-graph region with event-record NODES inside the graph instead:
@@ -432,7 +455,7 @@ class RegionClock(object):
             if self.settle_us > 0:
                 time.sleep(self.settle_us * 1e-6)
             t0 = time.perf_counter()
-            segs = self.runner.run(self.steps, before_first_launch=before, after_last_launch=after, clock=True)
+            segs = self.runner.run(steps, before_first_launch=before, after_last_launch=after, clock=True)
             self.drain(exchange)
             walls.append(time.perf_counter() - t0)
             self.rendezvous(exchange)
@@ -774,7 +797,7 @@ def main(argv=None):
     from aquaticgymenv_amd import presets
     obstacles = presets.NONE if args.no_obstacles else presets.BENCH8
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baselines(args, obstacles)          # before anything touches the GPU (see the docstring)
 
     # rank 0's ONE JSON line is the only thing this process may put on stdout: RCCL prints a version banner there when its
@@ -821,7 +844,10 @@ def main(argv=None):
                       auto_reset=0 if args.no_auto_reset else args.reset_mode, device=dev)
     env.reset()
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
-    chunk = min(CHUNK, max(args.steps, 1))
+    lens = args.region_steps                             # the timed regions' lengths: args.steps steps in all
+    region = lens[0]                                     # the longest region
+    lengths = sorted(set(lens), reverse=True)            # ... and the one or two lengths whose graphs are captured
+    chunk = min(CHUNK, region)
     if args.continuous:
         actions = torch.rand((CHUNK, 2, env.ld), device=dev, generator=gen) * 0.3 + 0.2
     else:
@@ -829,11 +855,11 @@ def main(argv=None):
     words = env.ld // 64
     # rows of one done-mask block = one all-gather: at most GATHER_EVERY chunks, and no more than a region holds (a
     # 20-step region must not ship a 500-row buffer through RCCL)
-    block_rows = max(chunk, min(GATHER_EVERY * CHUNK, args.steps))
+    block_rows = max(chunk, min(GATHER_EVERY * CHUNK, region))
     hist = [torch.zeros((block_rows, words), dtype=torch.int64, device=dev) for _ in range(2)]
     exchange, exchange_kind, exchange_note = None, None, args.exchange_note
-    slots = max([exchange_blocks(w, chunk, block_rows) for w in warmup_runs(args.warmup, args.steps)] +
-                [exchange_blocks(args.steps, chunk, block_rows), 1])
+    slots = max([exchange_blocks(w, chunk, block_rows) for w in warmup_runs(args.warmup, region)] +
+                [exchange_blocks(k, chunk, block_rows) for k in lengths] + [1])
     if world > 1 or args.force_exchange:
         if watchdog is not None:
             watchdog.stage = "setting up the done-mask exchange (--exchange %s)" % args.exchange
@@ -848,18 +874,19 @@ def main(argv=None):
     runner = StepRunner(env, actions, hist, exchange, use_graph=not args.eager, chunk=chunk,
                         launch_events=LaunchEvents() if args.region_clock == "launch" else None)
     runner.set_stream(launch_stream)                     # (torch's current stream since set_stream() above)
-    by_launch = runner.clocked_by_launch_events(args.steps)
+    by_launch = all(runner.clocked_by_launch_events(k) for k in lengths)
     if args.region_clock == "launch" and not by_launch:
-        raise SystemExit("--region-clock launch: a region of %d steps is more than one block of %d" % (args.steps, chunk))
-    warm = warmup_runs(args.warmup, args.steps)
+        raise SystemExit("--region-clock launch: a region of %d steps is more than one block of %d" % (region, chunk))
+    warm = warmup_runs(args.warmup, region)
     for w in warm:
         runner.prepare(w)
-    if by_launch:
-        runner.prepare_clocked(args.steps)
-    else:
-        runner.prepare(args.steps, timing=args.graph_node_events)
+    for k in lengths:
+        if by_launch:
+            runner.prepare_clocked(k)
+        else:
+            runner.prepare(k, timing=args.graph_node_events)
     # region 0 must not be the first launch of its graphs (see warmup_runs)
-    uploaded = 0 if by_launch else runner.upload_unplayed(args.steps, warm)
+    uploaded = 0 if by_launch else sum(runner.upload_unplayed(k, warm + lengths[:i]) for i, k in enumerate(lengths))
     first_replay = ("no graph" if (by_launch or not runner.use_graph) else
                     "warm-up" if not uploaded else "hipGraphUpload (%d graph%s the warm-up does not replay)" % (uploaded, "s" * (uploaded != 1)))
 
@@ -869,7 +896,7 @@ def main(argv=None):
         launch_ev.append(runner.launch_events.elapsed_ms() if by_launch else None)
         node_ms.append(runner.region_graph_ms(segs) if args.graph_node_events and not by_launch else None)
 
-    clock = RegionClock(runner, args.steps, torch=torch, dist=dist if distributed else None, stream=launch_stream,
+    clock = RegionClock(runner, region, torch=torch, dist=dist if distributed else None, stream=launch_stream,
                         settle_us=args.settle_us, on_region=diagnostics)
     for i, w in enumerate(warm):
         if i:
@@ -884,15 +911,18 @@ def main(argv=None):
     # (hipGraphUpload above is a set-up call, not steps).  Either way the line says so: config.untimed_steps_beyond_warmup
     untimed_beyond_warmup = 0
     if rolls_back_first_replay(args.first_replay, runner.use_graph, by_launch, args.regions):
-        rolled_back = runner.replay_unplayed_and_roll_back(args.steps, warm, repeats=args.ramp_replays)
-        torch.cuda.synchronize()
+        rolled_back = 0
+        for i, k in enumerate(lengths):
+            replayed = runner.replay_unplayed_and_roll_back(k, warm + lengths[:i], repeats=args.ramp_replays)
+            torch.cuda.synchronize()
+            if replayed:
+                rolled_back += replayed
+                untimed_beyond_warmup += k * max(1, args.ramp_replays)
         if rolled_back:
-            untimed_beyond_warmup = args.steps * max(1, args.ramp_replays)
             first_replay = ("one untimed replay rolled back to the state after the warm-up (%d graph%s the warm-up does not replay)"
                             % (rolled_back, "s" * (rolled_back != 1)))
     clock.rendezvous(exchange)
-    walls, events, segs = clock.run(args.regions, exchange)
-    my_events = list(events)
+    walls, events, segs = clock.run(args.regions, exchange, lengths=lens)
 
     def max_over_ranks(values):
         """the region's time is when the slowest rank was done"""
@@ -903,14 +933,18 @@ def main(argv=None):
         return [float(v) for v in tmax.cpu()]
 
     walls = max_over_ranks(walls)
+    # per step, region by region (the regions may differ in length by one step): seconds by wall clock, milliseconds by the
+    # events on the launch stream
+    wall_step = [w / k for w, k in zip(walls, lens)]
+    stream_step = [e / k for e, k in zip(events, lens)]
     per_rank = None
     if distributed:
         # every rank's own clocks: one slow GPU (or one slow link) shows here, not in a MAX
         per_rank = [None] * ranks_seen
         dist.all_gather_object(per_rank, {"rank": rank, "device": devices[rank] if rank < len(devices) else None,
-                                          "event_us_per_step": statistics.median(my_events) * 1e3 / args.steps,
-                                          "event_us_per_step_max": max(my_events) * 1e3 / args.steps})
-    timed_steps = args.regions * args.steps
+                                          "event_us_per_step": statistics.median(stream_step) * 1e3,
+                                          "event_us_per_step_max": max(stream_step) * 1e3})
+    timed_steps = sum(lens)
 
     # sanity on the timed work (no cached / skipped work): every step was queued, the worlds moved, and -- with
     # restarts on -- episodes ended inside the last timed region (reported, not asserted: a one-step region right
@@ -932,42 +966,44 @@ def main(argv=None):
                           "episodes_in_peer_blocks": peers}
         if not exchange_check["own_block_intact"]:
             raise RuntimeError("rank %d: the done-mask block it received from itself differs from the block it sent" % rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env, n, np)
 
     result = None
     if rank == 0:
         a_bytes = A_CONTINUOUS if args.continuous else A_DISCRETE
-        mid = pick_median(walls)
-        wall = walls[mid]
-        steps_per_s = world * n * args.steps / wall
+        wall = wall_step[pick_median(wall_step)]                      # s per step, the median region's
+        steps_per_s = world * n / wall
+        ev_step = [e / k for e, k in zip(launch_ev, lens)] if by_launch else stream_step
         # the step kernel is the only kernel in the timed stream: its average launch period on the launch stream
         # (HIP events around the region: inter-kernel boundaries and the event-to-first-kernel gap included, so
         # this is an upper bound of the kernel's own duration); median over the regions
         # (a one-block region carries its events ON its first and last launch instead: the two stream events are marker
         # packets of their own and read 12-14 us more per region than first kernel start -> last kernel end)
-        launch_s = statistics.median(launch_ev if by_launch else events) * 1e-3 / args.steps
+        launch_s = statistics.median(ev_step) * 1e-3
         achieved = a_bytes * n / launch_s / 1e9
-        first_s = statistics.median((launch_ev if by_launch else events)[:REGIONS]) * 1e-3 / args.steps
-        first_wall = statistics.median(walls[:REGIONS])
+        first_s = statistics.median(ev_step[:REGIONS]) * 1e-3
+        first_wall = statistics.median(wall_step[:REGIONS])
         traffic, traffic_src = committed_traffic(n, args)
         # `value` counts every world of the batch in every step.  With next-step restarts a world that finished at tick t
         # does not step during tick t + 1 (it is re-seeded and reports reward 0, term 0): those ticks are the episodes that
         # ended one tick earlier -- counted here from the last region's own done masks (rank 0's shard)
         restart_ticks = ended if (not args.no_auto_reset and args.reset_mode == 2) else 0
-        restart_frac = restart_ticks / float(max(args.steps * n, 1))
-        issue_us, issue_src = issue_bound(n, args, ended / float(max(args.steps, 1)))
+        restart_frac = restart_ticks / float(max(lens[-1] * n, 1))
+        issue_us, issue_src = issue_bound(n, args, ended / float(max(lens[-1], 1)))
         result = {
             "metric": "env-steps/sec at batch=262144; achieved HBM GB/s vs roofline; 1/2/4/8-GPU scaling",
             "value": steps_per_s, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": wall * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": wall * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             # the two clocks side by side, each rate beside the roofline fraction that follows from it (SURVEY.md 8d:
             # achieved = A x steps per second): value <-> roofline.frac_by_wall (wall clock, MAX over the ranks, barriers
             # between the regions); value_by_events <-> roofline.frac (HIP events on rank 0's launch stream)
             "value_by_events": world * n / launch_s,
             "regions": args.regions, "regions_rule": args.regions_rule, "regions_ms": [w * 1e3 for w in walls],
-            "region_reported": "median",
-            "regions_outliers": {"by_events": region_outliers([e * 1e3 / args.steps for e in (launch_ev if by_launch else events)]),
-                                 "by_wall": region_outliers([w * 1e6 / args.steps for w in walls])},
+            "region_steps": lens, "region_reported": "median",
+            "regions_outliers": {"by_events": region_outliers([e * 1e3 for e in ev_step]),
+                                 "by_wall": region_outliers([w * 1e6 for w in wall_step])},
             "config": {"workload": "batch %d worlds/GPU, %s actions, %s, waves on, auto-reset (%s), %s of <= %d steps"
                        % (n, "continuous f32x2" if args.continuous else "discrete u8",
                           "no obstacles" if args.no_obstacles else "4 circle + 4 rect obstacles",
@@ -988,7 +1024,7 @@ def main(argv=None):
                          "frac": achieved / HBM_PEAK_GBPS, "frac_of_measured_copy_peak": achieved / HBM_COPY_GBPS,
                          # ... on live world-steps only (a restart tick moves no boat: sanity.restart_ticks_fraction)
                          "frac_live": achieved / HBM_PEAK_GBPS * (1.0 - restart_frac),
-                         "frac_by_wall": a_bytes * n / (wall / args.steps) / 1e9 / HBM_PEAK_GBPS,
+                         "frac_by_wall": a_bytes * n / wall / 1e9 / HBM_PEAK_GBPS,
                          # the protocol-independent figure, the one to compare across rounds: the kernel's own average
                          # duration under rocprofv3 --kernel-trace with this command's flags, committed for THIS build
                          "kernel_only": kernel_only(n, args, a_bytes),
@@ -997,14 +1033,14 @@ def main(argv=None):
                          "issue_bound_us": issue_us, "issue_bound_source": issue_src,
                          "first_regions": {"n": min(REGIONS, args.regions), "launch_us": first_s * 1e6,
                                            "frac": a_bytes * n / first_s / 1e9 / HBM_PEAK_GBPS,
-                                           "ms_per_step": first_wall * 1e3 / args.steps,
-                                           "value": world * n * args.steps / first_wall,
+                                           "ms_per_step": first_wall * 1e3,
+                                           "value": world * n / first_wall,
                                            "what": "the same figures from the median of the FIRST %d regions alone" % min(REGIONS, args.regions)},
-                         "launch_us_regions": [e * 1e3 / args.steps for e in (launch_ev if by_launch else events)],
+                         "launch_us_regions": [e * 1e3 for e in ev_step],
                          "launch_us_events": "launch" if by_launch else "stream",
-                         "launch_us_stream_events_regions": [e * 1e3 / args.steps for e in events],
-                         "frac_by_stream_events": a_bytes * n / (statistics.median(events) * 1e-3 / args.steps) / 1e9 / HBM_PEAK_GBPS,
-                         "launch_us_graph_nodes_regions": ([g * 1e3 / args.steps if g else None for g in node_ms]
+                         "launch_us_stream_events_regions": [e * 1e3 for e in stream_step],
+                         "frac_by_stream_events": a_bytes * n / (statistics.median(stream_step) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                         "launch_us_graph_nodes_regions": ([g * 1e3 / k if g else None for g, k in zip(node_ms, lens)]
                                                            if args.graph_node_events else None),
                          "note": ("launch_us = HIP-event time of a timed region / its launches, median region, inter-kernel "
                                   "boundaries included.  The two events are ATTACHED to the region's first launch (its start time) "
@@ -1026,9 +1062,9 @@ def main(argv=None):
             result["host"] = host_info()
         if per_rank is not None:
             result["per_rank"] = per_rank
-        if args.extras and world == 1:
+        if (args.extras or args.full) and world == 1:
             result["extras"] = extras(env, torch, n, a_bytes)
-        if args.per_world_tables and world == 1:
+        if (args.per_world_tables or args.full) and world == 1:
             result.setdefault("extras", {})["per_world_tables"] = per_world_tables(torch, np, presets, BatchedAqua, n, dev)
 
     # ---- the line goes out exactly once, whatever the optional legs below do
@@ -1046,11 +1082,11 @@ def main(argv=None):
     if (exchange is not None or world > 1) and not args.no_exchange_ab:
         a_bytes = A_CONTINUOUS if args.continuous else A_DISCRETE
         ab = {"regions_per_leg": args.ab_regions, "main": exchange_kind or "none",
-              "what": "regions of the same K steps behind the main ones: step_only = no exchange at all; ipc / rccl = the "
+              "what": "regions as long as the longest main one, behind the main ones: step_only = no exchange at all; ipc / rccl = the "
                       "transport the main regions did not use (the main one's figures are the line's own, copied here)"}
         if rank == 0:
             result.setdefault("extras", {})["exchange_ab"] = ab
-            ab[exchange_kind or "none"] = dict(summarize_regions(walls, events, args.steps, n, world, a_bytes),
+            ab[exchange_kind or "none"] = dict(summarize_regions(wall_step, stream_step, 1, n, world, a_bytes),
                                                own_block_intact=(exchange_check or {}).get("own_block_intact"),
                                                episodes_in_peer_blocks=(exchange_check or {}).get("episodes_in_peer_blocks"))
 
@@ -1082,7 +1118,7 @@ def main(argv=None):
                     "episodes_in_peer_blocks": [int(popcount_words(got[r].cpu().numpy(), np)) for r in range(ranks_seen) if r != rank]}
 
         def summarize_leg(leg_walls, leg_events):
-            return summarize_regions(max_over_ranks(leg_walls), leg_events, args.steps, n, world, a_bytes)
+            return summarize_regions(max_over_ranks(leg_walls), leg_events, region, n, world, a_bytes)
 
         def agree_leg(error, what):
             from aquaticgymenv_amd.sharded import agree
@@ -1114,6 +1150,24 @@ def main(argv=None):
         dist.destroy_process_group()
         teardown.cancel()
     return result
+
+
+def dump_outputs(out_dir, env, n, np):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the observation [n][5] and the wave
+    [n][2] (views of the state), the last step's reward and termination code, the worlds' step counters -- as float32
+    out_dir/<name>.npy.  Past DUMP_LIMIT_BYTES in all: the same seeded, sorted sample of worlds from every array, its indices
+    in out_dir/world_index.npy (float64)."""
+    arrays = {"obs": env.obs, "wave": env.wave, "reward": env.reward[:n], "term": env.term[:n], "time": env.time[:n]}
+    per_world = 4 * sum(int(np.prod(arrays[name].shape[1:])) for name in DUMPED_ARRAYS)
+    index = None
+    if n * per_world > DUMP_LIMIT_BYTES:
+        index = np.sort(np.random.RandomState(0).choice(n, DUMP_LIMIT_BYTES // (per_world + 8), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMPED_ARRAYS:
+        a = arrays[name].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if index is None else a[index]))
+    if index is not None:
+        np.save(os.path.join(out_dir, "world_index.npy"), index.astype(np.float64))
 
 
 def library_tag():

@@ -11,6 +11,8 @@ import sys
 
 import pytest
 
+import bench                                    # (host logic only: importing it touches no GPU)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -34,6 +36,22 @@ def _run(cmd, timeout=900, faults=None):
     return json.loads(lines[0])
 
 
+def _unplayed_lengths(steps, warmup):
+    """the region lengths whose graphs the warm-up does not all replay (bench.main: uploaded, and rolled back below 20
+    regions), longest first; a length counts once its graphs have been replayed"""
+    lens = bench.split_steps(steps, min(bench.REGIONS, steps))
+    chunk = min(bench.CHUNK, lens[0])
+    rows = max(chunk, min(bench.GATHER_EVERY * bench.CHUNK, lens[0]))
+    played = set(seg[:3] for w in bench.warmup_runs(warmup, lens[0]) for seg in bench.plan_region(w, chunk, rows))
+    out = []
+    for k in sorted(set(lens), reverse=True):
+        keys = [seg[:3] for seg in bench.plan_region(k, chunk, rows)]
+        if any(key not in played for key in keys):
+            out.append(k)
+        played.update(keys)
+    return out
+
+
 def _check_line(r, steps, warmup, n_gpus=1, envs=262144, timings_mean_something=True, clock=None):
     clock = clock or "stream"                                      # bench.py's default --region-clock
     assert r["steps"] == steps and r["warmup"] == warmup and r["n_gpus"] == n_gpus
@@ -43,9 +61,11 @@ def _check_line(r, steps, warmup, n_gpus=1, envs=262144, timings_mean_something=
     assert r["config"]["baseline_config"] == "configs[2]" and str(envs) in r["config"]["workload"]
     assert r["config"]["ranks_seen"] == n_gpus and len(r["config"]["devices"]) == n_gpus
     assert r["config"]["launch"] == ("eager" if clock == "launch" else "hipGraph")
-    regions = max(5, -(-2000 // steps))              # bench.regions_for(): five at least, 2 000 timed steps at least
-    assert len(r["regions_ms"]) == r["regions"] == regions and r["regions_rule"].startswith("max(5")
-    assert sorted(r["regions_ms"])[(regions - 1) // 2] == pytest.approx(r["ms_per_step"] * steps)
+    regions = min(5, steps)                          # --steps timed steps in all, split into five regions
+    lens = [steps // regions + (i < steps % regions) for i in range(regions)]
+    assert len(r["regions_ms"]) == r["regions"] == regions and r["regions_rule"].startswith("min(5")
+    assert r["region_steps"] == lens and sum(lens) == steps
+    assert sorted(m / k for m, k in zip(r["regions_ms"], lens))[(regions - 1) // 2] == pytest.approx(r["ms_per_step"])
     roof = r["roofline"]
     assert roof["bound"] == "hbm" and roof["peak"] == 8000.0 and roof["unit"] == "GB/s"
     assert roof["frac"] == pytest.approx(roof["achieved"] / roof["peak"])
@@ -53,7 +73,7 @@ def _check_line(r, steps, warmup, n_gpus=1, envs=262144, timings_mean_something=
     assert roof["launch_us_events"] == clock and len(roof["launch_us_regions"]) == regions
     assert len(roof["launch_us_stream_events_regions"]) == regions and 0.0 < roof["frac_by_stream_events"] < 1.0
     first = roof["first_regions"]                      # the first five regions on their own
-    assert first["n"] == 5 and first["frac"] == pytest.approx(62 * envs / (first["launch_us"] * 1e-6) / 1e9 / 8000.0)
+    assert first["n"] == min(5, regions) and first["frac"] == pytest.approx(62 * envs / (first["launch_us"] * 1e-6) / 1e9 / 8000.0)
     assert first["launch_us"] == pytest.approx(sorted(roof["launch_us_regions"][:5])[2])
     if clock == "launch" and timings_mean_something:
         # first kernel start -> last kernel end lies INSIDE the two stream events recorded around the same launches
@@ -63,18 +83,19 @@ def _check_line(r, steps, warmup, n_gpus=1, envs=262144, timings_mean_something=
         assert roof["launch_us_regions"] == roof["launch_us_stream_events_regions"]
     assert (0.05 if timings_mean_something else 0.0) < roof["frac"] < 1.0
     assert "traffic" in roof and "traffic_source" in roof
-    assert r["sanity"]["steps_queued"] == warmup + regions * steps
+    assert r["sanity"]["steps_queued"] == warmup + steps
     assert r["sanity"]["episodes_ended_last_region"] > 0
     # what `value` counts: every world in every step; the restart ticks of the next-step mode are reported beside it
     frac = r["sanity"]["restart_ticks_fraction"]
-    assert frac == pytest.approx(r["sanity"]["episodes_ended_last_region"] / float(steps * envs)) and 0.0 < frac < 0.1
+    assert frac == pytest.approx(r["sanity"]["episodes_ended_last_region"] / float(lens[-1] * envs)) and 0.0 < frac < 0.1
     assert r["sanity"]["live_world_steps_per_s"] == pytest.approx(r["value"] * (1.0 - frac))
     # a timed graph the warm-up does not replay: replayed once untimed and taken back only where region 0 could move the
     # median (fewer than 20 regions); the line says how many steps ran beyond the W warm-up steps
-    rolled = warmup < steps and regions < 20 and clock != "launch"
+    unplayed = _unplayed_lengths(steps, warmup)
+    rolled = bool(unplayed) and regions < 20 and clock != "launch"
     assert r["config"]["timed_graph_first_replay"].startswith(
-        "one untimed replay rolled back" if rolled else ("hipGraphUpload" if warmup < steps else "warm-up")) or clock == "launch"
-    assert r["config"]["untimed_steps_beyond_warmup"] == (steps if rolled else 0)
+        "one untimed replay rolled back" if rolled else ("hipGraphUpload" if unplayed else "warm-up")) or clock == "launch"
+    assert r["config"]["untimed_steps_beyond_warmup"] == (sum(unplayed) if rolled else 0)
     assert "issue_bound_us" in roof and "issue_bound_source" in roof
     # one coherent line (round 5): each rate beside the fraction that follows from it, achieved = A x steps per second
     assert roof["frac"] == pytest.approx(62 * r["value_by_events"] / n_gpus / 1e9 / 8000.0)
@@ -90,9 +111,14 @@ def _check_line(r, steps, warmup, n_gpus=1, envs=262144, timings_mean_something=
 
 @pytest.mark.gpu
 def test_bench_with_the_drivers_flags_in_a_child_process():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (round 1's driver command, which asserted) prints the line"""
-    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"])
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` (round 1's driver command, which asserted) prints the line, and
+    does nothing else: the CPU baselines and the extra kernels' lines come with --full"""
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
     _check_line(r, 20, 5)
+    assert not [k for k in r if k.startswith("cpu_baseline")] and "extras" not in r and "host" not in r
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--full"])
+    _check_line(r, 20, 5)
+    assert set(r["extras"]) == {"fused_rollout", "per_world_tables"} and r["extras"]["fused_rollout"]["env_steps_per_s"] > 0
     for key in ("cpu_baseline", "cpu_baseline_1core", "cpu_baseline_c"):
         b = r[key]
         assert b["value"] > 0 and b["unit"] == "env-steps/s" and b["kind"] == "port" and b["cores"] >= 1 and b["sample"]
@@ -101,11 +127,32 @@ def test_bench_with_the_drivers_flags_in_a_child_process():
 
 @pytest.mark.gpu
 def test_bench_odd_step_counts_in_a_child_process():
-    """one step without warm-up, and a count that needs full chunks + a remainder"""
+    """one step without warm-up, a count that needs full chunks + a remainder, and regions of two lengths"""
     r = _run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
-    assert r["steps"] == 1 and r["regions"] == 400 and r["sanity"]["steps_queued"] == 400      # (bench.MAX_REGIONS one-step regions)
+    assert r["steps"] == 1 and r["regions"] == 1 and r["sanity"]["steps_queued"] == 1 and r["region_steps"] == [1]
     r = _run([sys.executable, "bench.py", "--steps", "230", "--warmup", "7", "--no-cpu-baseline"])
     _check_line(r, 230, 7)
+    r = _run([sys.executable, "bench.py", "--steps", "23", "--warmup", "5"])     # regions of 5 and 4 steps: the warm-up
+    _check_line(r, 23, 5)                                                        # replays the 5-step graph, not the 4-step one
+    assert r["region_steps"] == [5, 5, 5, 4, 4] and r["config"]["untimed_steps_beyond_warmup"] == 4
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_step_of_the_timed_path(tmp_path):
+    """--dump-outputs: the same arguments give the same arrays, run after run; one more timed step gives others"""
+    import numpy as np
+    runs = []
+    for d, steps in (("a", 20), ("b", 20), ("c", 21)):
+        r = _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(tmp_path / d)])
+        assert r["steps"] == steps and r["sanity"]["steps_queued"] == 5 + steps
+        runs.append({name: np.load(str(tmp_path / d / (name + ".npy"))) for name in ("obs", "wave", "reward", "term", "time")})
+    a, b, c = runs
+    assert {k: v.shape for k, v in a.items()} == {"obs": (262144, 5), "wave": (262144, 2), "reward": (262144,),
+                                                   "term": (262144,), "time": (262144,)}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert set(np.unique(a["term"])) <= {0.0, 1.0, 2.0, 3.0} and 0 < int((a["term"] != 0).sum()) < 262144 // 10
+    assert all(np.array_equal(a[k], b[k]) for k in a), "same arguments, same inputs: the outputs must be identical"
+    assert not np.array_equal(a["obs"], c["obs"])
 
 
 @pytest.mark.gpu
@@ -116,13 +163,13 @@ def test_bench_diagnostic_flags_in_a_child_process():
               "--copy-engine", "dma", "--graph-node-events", "--settle-us", "100"])
     _check_line(r, 20, 5)
     nodes = r["roofline"]["launch_us_graph_nodes_regions"]
-    assert len(nodes) == 100 and all(v and v > 1.0 for v in nodes)
+    assert len(nodes) == 5 and all(v and v > 1.0 for v in nodes)
     assert r["config"]["done_mask_exchange_kind"] == "ipc" and r["config"]["done_mask_copy_engine"] == "dma"
     assert r["sanity"]["done_mask_exchange_last_block"]["own_block_intact"] is True
     r = _run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--region-clock", "launch"])
     _check_line(r, 20, 5, clock="launch")               # the events attached to the region's first and last launch
     r = _run([sys.executable, "bench.py", "--steps", "30", "--warmup", "3", "--no-cpu-baseline", "--eager"])
-    assert r["config"]["launch"] == "eager" and r["steps"] == 30 and r["sanity"]["steps_queued"] == 3 + 67 * 30
+    assert r["config"]["launch"] == "eager" and r["steps"] == 30 and r["sanity"]["steps_queued"] == 3 + 30
 
 
 @pytest.mark.gpu
@@ -172,13 +219,13 @@ def test_two_ranks_time_the_step_path_alone_and_the_other_transport_behind_the_m
     _check_line(r, 20, 5, n_gpus=2, envs=65536, timings_mean_something=False)
     ab = r["extras"]["exchange_ab"]
     assert ab["main"] == "ipc" and ab["regions_per_leg"] == 25 and "error" not in ab
-    assert ab["ipc"]["regions"] == 100 and ab["ipc"]["own_block_intact"] is True
+    assert ab["ipc"]["regions"] == r["regions"] and ab["ipc"]["own_block_intact"] is True
     assert ab["ipc"]["value"] == pytest.approx(r["value"]) and ab["ipc"]["frac"] == pytest.approx(r["roofline"]["frac"])
     so = ab["step_only"]
     assert so["regions"] == 25 and so["value"] > 0 and so["event_us_per_step"] > 0 and "own_block_intact" not in so
     assert "RCCL refuses two ranks on one device" in ab["rccl"]["error"] and ab["rccl"]["error"].startswith("set-up:")
     assert [p["rank"] for p in r["per_rank"]] == [0, 1] and all(p["event_us_per_step"] > 0 and "cuda:0" in p["device"] for p in r["per_rank"])
-    assert r["sanity"]["steps_queued"] == 5 + 100 * 20          # the line's own regions; the legs ran behind them
+    assert r["sanity"]["steps_queued"] == 5 + 20                # the line's own regions; the legs ran behind them
 
 
 @pytest.mark.gpu

@@ -176,13 +176,21 @@ def test_median_pick():
 
 def test_argument_checks():
     assert bench.parse(["--steps", "20", "--warmup", "5"]).steps == 20
-    assert bench.parse([]).regions == bench.REGIONS and bench.parse([]).regions_rule.startswith("max(5")
-    # five regions at least, and at least one default region's worth of timed steps in all
-    assert bench.parse(["--steps", "20", "--warmup", "5"]).regions == 100 and bench.regions_for(1) == bench.MAX_REGIONS
+    assert bench.parse([]).regions == bench.REGIONS and bench.parse([]).regions_rule.startswith("min(5")
+    # --steps is the number of timed steps: five regions that hold exactly that many (fewer regions below five steps)
+    for steps in (1, 2, 4, 5, 7, 20, 230, 2000, 100003):
+        a = bench.parse(["--steps", str(steps), "--warmup", "5"])
+        assert a.regions == min(5, steps) == len(a.region_steps) and sum(a.region_steps) == steps
+        assert max(a.region_steps) - min(a.region_steps) <= 1 and a.region_steps == sorted(a.region_steps, reverse=True)
+    assert bench.parse(["--steps", "20", "--warmup", "5"]).region_steps == [4] * 5
+    assert bench.parse(["--steps", "7"]).region_steps == [2, 2, 1, 1, 1]
+    # the extra legs of an N > 1 run: five regions at least, and at least 2 000 timed steps in all
+    assert bench.regions_for(1) == bench.MAX_REGIONS
     assert [bench.regions_for(k) for k in (20, 100, 399, 400, 401, 2000, 100000)] == [100, 20, 6, 5, 5, 5, 5]
     explicit = bench.parse(["--steps", "20", "--regions", "7"])
-    assert explicit.regions == 7 and explicit.regions_rule == "--regions"
-    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--regions", "0"], ["--region-clock", "auto"]):
+    assert explicit.regions == 7 and explicit.regions_rule == "--regions" and explicit.region_steps == [3] * 6 + [2]
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--regions", "0"], ["--steps", "3", "--regions", "4"],
+                ["--region-clock", "auto"]):
         with pytest.raises(SystemExit):
             bench.parse(bad)
     assert bench.parse([]).region_clock == "stream"          # the graph between two recorded stream events is the default clock
@@ -404,10 +412,14 @@ def test_every_fraction_sits_beside_the_rate_it_follows_from():
 
 def test_the_untimed_replay_is_dropped_where_region_zero_cannot_move_the_median():
     assert bench.rolls_back_first_replay("rollback", True, False, 5)
-    assert not bench.rolls_back_first_replay("rollback", True, False, bench.regions_for(20))     # the driver's command: 100 regions
+    assert not bench.rolls_back_first_replay("rollback", True, False, bench.regions_for(20))     # 100 regions
     assert not bench.rolls_back_first_replay("upload", True, False, 5)
     assert not bench.rolls_back_first_replay("rollback", False, False, 5) and not bench.rolls_back_first_replay("rollback", True, True, 5)
-    assert bench.parse(["--steps", "20"]).ab_regions == 100 and bench.parse([]).ab_regions == bench.AB_MIN_REGIONS
+    # the extra legs time regions as long as the longest main region: enough of them for 2 000 steps (at most MAX_REGIONS)
+    assert bench.parse(["--steps", "20"]).ab_regions == bench.regions_for(4) == bench.MAX_REGIONS
+    assert bench.parse(["--steps", "2000"]).ab_regions == bench.AB_MIN_REGIONS           # 5 regions of 400: 20 legs' regions
+    assert bench.parse(["--steps", "500"]).ab_regions == 20 and bench.parse(["--steps", "100"]).ab_regions == 100
+    assert bench.parse([]).ab_regions == bench.AB_MIN_REGIONS
     assert bench.parse(["--ab-regions", "3"]).ab_regions == 3
 
 
@@ -434,6 +446,12 @@ def test_region_clock_counts_and_brackets_on_the_cpu():
     r.exchange = None
     clock.run(2, None)
     assert env._tick == 100 and ex.log == []
+    # regions of the given lengths (bench.split_steps): exactly their sum is queued
+    r.prepare(19)
+    walls, events, segs = clock.run(3, None, lengths=[20, 19, 19])
+    assert env._tick == 158 and r.steps_run == 158 and len(walls) == 3 and segs[-1][2] == 19
+    with pytest.raises(ValueError):
+        clock.run(2, None, lengths=[20])
 
 
 class _Guard(object):
@@ -493,3 +511,39 @@ def test_exchange_ab_bookkeeping_never_touches_what_was_measured():
     assert r.exchange is main                                                      # ... and the runner is back on the main transport
     assert env._tick == r.steps_run == 2 * 20 * 2 + 20                             # two legs ran 2 regions; the broken one's first region
     assert guard.stages[0] == "exchange_ab leg 'step_only': set-up" and "exchange_ab leg 'rccl': closing its exchange" in guard.stages
+
+
+# ------------------------------------------------------------------ --dump-outputs
+class _DumpEnv(object):
+    """what bench.dump_outputs reads of a BatchedAqua, as CPU tensors"""
+
+    def __init__(self, n):
+        import torch
+        ld = -(-n // 64) * 64
+        self.state = torch.arange(7 * ld, dtype=torch.float32).reshape(7, ld)
+        self.obs, self.wave = self.state[:5, :n].t(), self.state[5:7, :n].t()
+        self.reward = torch.linspace(-1.0, 1.0, ld)
+        self.term = (torch.arange(ld) % 4).to(torch.uint8)
+        self.time = torch.arange(ld, dtype=torch.int32)
+
+
+def test_dump_outputs_writes_float32_arrays_and_samples_past_the_limit(tmp_path, monkeypatch):
+    n = 1000
+    env = _DumpEnv(n)
+    bench.dump_outputs(str(tmp_path / "all"), env, n, np)
+    got = {name: np.load(str(tmp_path / "all" / (name + ".npy"))) for name in bench.DUMPED_ARRAYS}
+    assert {k: v.shape for k, v in got.items()} == {"obs": (n, 5), "wave": (n, 2), "reward": (n,), "term": (n,), "time": (n,)}
+    assert all(v.dtype == np.float32 for v in got.values()) and not (tmp_path / "all" / "world_index.npy").exists()
+    assert np.array_equal(got["obs"], env.obs.numpy()) and np.array_equal(got["time"], np.arange(n, dtype=np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (10 * 4 + 8))          # room for 100 worlds and their indices
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), env, n, np)
+    idx = np.load(str(tmp_path / "s1" / "world_index.npy"))
+    assert idx.dtype == np.float64 and idx.shape == (100,) and np.all(np.diff(idx) > 0)
+    total = 0
+    for name in bench.DUMPED_ARRAYS + ("world_index",):
+        a, b = np.load(str(tmp_path / "s1" / (name + ".npy"))), np.load(str(tmp_path / "s2" / (name + ".npy")))
+        assert np.array_equal(a, b), "the sample must be the same from run to run"
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "obs.npy")), env.obs.numpy()[idx.astype(np.int64)])

@@ -1,6 +1,7 @@
 """TensorFlow-free SavedModel variable reader (aquaticgymenv_amd/tf_import.py): round trip through a tensor
-bundle written by this test (same on-disk format: SSTable index + raw data shard), and -- only where the
-reference tree is mounted -- the reference's own two checkpoints against the committed fixture."""
+bundle written by this test (same on-disk format: SSTable index + raw data shard), and the reference's two
+trained policies (the committed fixture tests/golden/dqn_policies.npz) through bundles in the layout its Keras
+checkpoints have."""
 import os
 import struct
 
@@ -51,6 +52,10 @@ def _write_bundle(path, tensors):
     os.makedirs(path, exist_ok=True)
     data, entries = bytearray(), [(b"", b"\x08\x01")]        # header entry under the empty key
     for key in sorted(tensors):
+        if isinstance(tensors[key], bytes):                  # DT_STRING (the object-graph proto): the reader skips it
+            entries.append((key.encode(), _entry(7, (), len(data), len(tensors[key]))))
+            data += tensors[key]
+            continue
         arr = np.asarray(tensors[key])
         dt = {np.dtype(np.float32): 1, np.dtype(np.int64): 9}[arr.dtype]
         entries.append((key.encode(), _entry(dt, arr.shape, len(data), arr.nbytes)))
@@ -93,12 +98,28 @@ def test_round_trip(tmp_path):
         read_checkpoint(str(tmp_path))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/example_policies"), reason="reference tree not mounted")
-def test_reference_checkpoints_equal_the_fixture():
+def test_checkpoints_in_the_references_layout_equal_the_fixture(tmp_path):
+    """the reference's two trained policies as its Keras checkpoints hold them (main/impl/dqn.py:316-321): kernel and bias
+    of every dense layer, Adam's two slots per variable, the optimizer's int64 counters and the object-graph string entry
+    -- written from the committed weights, read back bit for bit, the layers in order"""
     z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dqn_policies.npz"))
-    for tag, sub in (("no_obs", "example_no_obs/models/model-00030"), ("with_obs", "example_with_obs/models/model-00032")):
-        layers = dense_stack(read_checkpoint(os.path.join("/root/reference/example_policies", sub, "variables")))
-        assert len(layers) == 3
+    rng = np.random.RandomState(1)
+    for tag in ("no_obs", "with_obs"):
+        tensors = {"_CHECKPOINTABLE_OBJECT_GRAPH": b"\x0a\x10object graph proto",
+                   "optimizer/iter/.ATTRIBUTES/VARIABLE_VALUE": np.array(30000, dtype=np.int64)}
+        for li in range(3):
+            for part in ("kernel", "bias"):
+                w = z["%s_%s%d" % (tag, part, li)]
+                tensors["layer_with_weights-%d/%s/.ATTRIBUTES/VARIABLE_VALUE" % (li, part)] = w
+                for slot in ("m", "v"):
+                    tensors["layer_with_weights-%d/%s/.OPTIMIZER_SLOT/optimizer/%s/.ATTRIBUTES/VARIABLE_VALUE"
+                            % (li, part, slot)] = rng.randn(*w.shape).astype(np.float32)
+        path = tmp_path / tag
+        _write_bundle(str(path), tensors)
+        got = read_checkpoint(str(path))
+        assert "_CHECKPOINTABLE_OBJECT_GRAPH" not in got and len(got) == 3 * 2 * 3 + 1
+        layers = dense_stack(got)
+        assert [k.shape for k, _ in layers] == [(5, 64), (64, 64), (64, 3)]
         for li, (k, b) in enumerate(layers):
             assert np.array_equal(k, z["%s_kernel%d" % (tag, li)]) and np.array_equal(b, z["%s_bias%d" % (tag, li)])
     assert abs(z["no_obs_published_success"].mean() - 0.938) < 1e-9 and abs(z["with_obs_published_success"].mean() - 0.667) < 1e-9
