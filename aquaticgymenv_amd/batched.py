@@ -104,8 +104,9 @@ class RolloutGraph(object):
             # the tick-base refresh and the clipped-action count are small torch operations: they must be ordered ahead of the
             # replay, so they go to the stream the replay goes to (torch's current one unless the caller named another)
             torch = env.torch
-            other = stream is not None and stream.value != torch.cuda.current_stream(env.device).cuda_stream
-            ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream.value, device=env.device)) if other else _NO_CONTEXT
+            sv = (stream.value or 0) if stream is not None else None     # (c_void_p(0).value is None: the null stream)
+            other = stream is not None and sv != torch.cuda.current_stream(env.device).cuda_stream
+            ctx = torch.cuda.stream(torch.cuda.ExternalStream(sv, device=env.device)) if other else _NO_CONTEXT
             with ctx:
                 if env._device_tick != env._tick:
                     env._sync_device_tick()

@@ -404,6 +404,28 @@ void aqua_oracle_reset_tables(int64_t n, int K, const double* obst_all, int wave
     }
 }
 
+/* ------------------------------------------------- sampled actions */
+/*
+ * The actions the device samples for worlds [env_offset, env_offset + n) at `tick` (AQUA_ACT_SAMPLE_D / _C), from the
+ * same Philox stream-4 words and with the same arithmetic as the sampled branch of aqua_oracle_rollout_f32 below:
+ * continuous == 0 -> uint8 out[n], the discrete index; else float32 out[2][n], vL then vR in [0.2, 0.5).  Fed back as
+ * stored actions (kind 0 / 3) they let any oracle entry point check a kernel that sampled them.
+ */
+void aqua_oracle_sample_actions(int64_t n, int continuous, uint64_t seed, uint64_t tick, int64_t env_offset, void* out)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t aw[2];
+        action_words(seed, (uint64_t)(env_offset + i), tick, aw);
+        if (continuous) {
+            float* f = (float*)out;
+            f[i] = fmaf(0.3f, u01f(aw[0]), 0.2f);
+            f[n + i] = fmaf(0.3f, u01f(aw[1]), 0.2f);
+        } else {
+            ((uint8_t*)out)[i] = (uint8_t)(((uint64_t)(aw[0] >> 8) * 3u) >> 24);
+        }
+    }
+}
+
 /* ------------------------------------------------- float32-state rollout */
 /*
  * The batched build stores its state in float32.  This drives step_one() from float32 storage

@@ -91,6 +91,9 @@ class COracle(object):
                                              ctypes.POINTER(ctypes.c_uint32)]
         L.aqua_oracle_step_noise.restype = None
         L.aqua_oracle_threads.restype = ctypes.c_int
+        L.aqua_oracle_sample_actions.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_int64, ctypes.c_void_p]
+        L.aqua_oracle_sample_actions.restype = None
 
     def threads(self):
         return int(self.lib.aqua_oracle_threads())
@@ -106,6 +109,14 @@ class COracle(object):
         raw = (ctypes.c_uint32 * 4)()
         self.lib.aqua_oracle_step_noise(seed, env, tick, u, raw)
         return np.array([u[0], u[1]]), [int(v) for v in raw]
+
+    def sample_actions(self, n, continuous=False, seed=0, tick=0, env_offset=0):
+        """the actions the device samples (policy 'random') for worlds [env_offset, env_offset + n) at `tick`, as stored
+        actions: uint8 [n] discrete indices, or float32 [2][n] thrusts (continuous)"""
+        out = np.empty((2, n), dtype=np.float32) if continuous else np.empty(n, dtype=np.uint8)
+        self.lib.aqua_oracle_sample_actions(int(n), int(bool(continuous)), int(seed), int(tick), int(env_offset),
+                                            out.ctypes.data_as(ctypes.c_void_p))
+        return out
 
     @staticmethod
     def _action(action):

@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 from tests._golden import StepGolden, load_reset, angle_diff
+from tests._parity import (TOL, _make, _host_state, _rollout_against_oracle, _buffered_rollout_against_oracle,
+                           _oracle_next_step_tables, _bearing_np)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -34,16 +34,6 @@ def capi():
 @pytest.fixture(scope="module")
 def golden():
     return StepGolden()
-
-
-def _make(torch, n, cfg_or_rows, continuous=False, waves=1, seed=1234, auto_reset=False, env_offset=0, **kw):
-    from aquaticgymenv_amd.batched import BatchedAqua
-    return BatchedAqua(n, obstacles=cfg_or_rows, waves=bool(waves), continuous=continuous, seed=seed,
-                       auto_reset=auto_reset, env_offset=env_offset, device="cuda:0", **kw)
-
-
-def _host_state(env):
-    return env.state[:, : env.num_envs].cpu().numpy(), env.time[: env.num_envs].cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -229,86 +219,6 @@ def test_step_matches_oracle_philox(torch, oracle, n, continuous, obst):
             a_or = a
         torch.cuda.synchronize()
         _compare_with_oracle(torch, oracle, env, state0, time0, a_or, reward.cpu().numpy(), term.cpu().numpy(), tick)
-
-
-def _rollout_against_oracle(torch, oracle, rows, n, steps, continuous, mode, env_offset, seed=99):
-    """device-sampled actions + restart of finished worlds against the oracle's float32-state rollout, teacher-forced
-    per step (the oracle restarts from the kernel's state every step).  Returns the number of finished episodes."""
-    env = _make(torch, n, rows, continuous=continuous, seed=seed, auto_reset=mode, env_offset=env_offset)
-    env.reset()
-    finished = 0
-    for it in range(steps):
-        s0, t0 = _host_state(env)
-        tick = env._tick
-        obs, reward, term = env.step(sample_actions=True)
-        torch.cuda.synchronize()
-        st = np.ascontiguousarray(s0.copy())
-        tt = t0.copy()
-        ep, o_rew, o_term, counts = oracle.rollout_f32(st, tt, 1, obstacles=env.obstacle_rows, waves=1,
-                                                        continuous=continuous, seed=env.seed, tick0=tick,
-                                                        env_offset=env_offset, auto_reset=mode)
-        k_state, k_time = _host_state(env)
-        term_h, rew_h = term.cpu().numpy(), reward.cpu().numpy()
-        assert np.array_equal(term_h, o_term)
-        assert np.max(np.abs(rew_h - o_rew)) <= TOL
-        assert np.array_equal(k_time, tt)
-        assert np.array_equal(env.done_mask().cpu().numpy(), (o_term != 0).astype(np.uint8))
-        reseeded = (o_term != 0) if mode == 1 else (t0 == -1 - ((tick - 1) & 1))
-        # worlds that restarted: float32 reset specification, bit for bit
-        assert np.array_equal(k_state[:, reseeded], st[:, reseeded])
-        if mode == 2:
-            assert np.all(rew_h[reseeded] == 0) and np.all(term_h[reseeded] == 0)
-            assert np.all(k_time[reseeded] == -3 - (tick & 1))        # restarted this tick, steps from 0 next tick
-            assert np.all(k_time[o_term != 0] == -1 - (tick & 1))     # marker carries the finishing tick's parity
-        live = ~reseeded
-        if live.any():
-            assert np.max(np.abs(k_state[0:2, live] - st[0:2, live])) <= TOL
-            assert np.max(angle_diff(k_state[2, live], st[2, live])) <= TOL
-            assert np.max(np.abs(k_state[5:7, live] - st[5:7, live])) <= 1e-7
-            assert np.array_equal(k_state[3:5, live], st[3:5, live])
-        finished += int((o_term != 0).sum())
-    return finished
-
-
-def _buffered_rollout_against_oracle(torch, oracle, rows, n, steps, continuous, mode, seed=31):
-    """the benchmark's own form -- actions from a pre-generated device buffer (uint8 indices / float32 [2][ld] thrusts,
-    bench.py), restart of finished worlds inside the step -- against the oracle's float32-state step, teacher-forced"""
-    env = _make(torch, n, rows, continuous=continuous, seed=seed, auto_reset=mode)
-    env.reset()
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    if continuous:   # U[0.15, 0.55): some thrusts outside the box, clipped as aqua.py:145-150 clips them
-        acts = torch.rand((steps, 2, env.ld), device="cuda:0", generator=g) * 0.4 + 0.15
-    else:
-        acts = torch.randint(0, 3, (steps, env.ld), device="cuda:0", generator=g, dtype=torch.int64).to(torch.uint8)
-    finished = restarted = 0
-    for it in range(steps):
-        s0, t0 = _host_state(env)
-        tick = env._tick
-        obs, reward, term = env.step(acts[it], soa=True) if continuous else env.step(acts[it][:n])
-        torch.cuda.synchronize()
-        st, tt = np.ascontiguousarray(s0.copy()), t0.copy()
-        a_host = acts[it][:, :n].cpu().numpy() if continuous else acts[it][:n].cpu().numpy()
-        ep, o_rew, o_term, counts = oracle.rollout_f32(st, tt, 1, obstacles=env.obstacle_rows, waves=1, continuous=continuous,
-                                                        actions=np.ascontiguousarray(a_host), seed=env.seed, tick0=tick,
-                                                        auto_reset=mode)
-        k_state, k_time = _host_state(env)
-        term_h, rew_h = term.cpu().numpy(), reward.cpu().numpy()
-        assert np.array_equal(term_h, o_term), "termination codes differ at step %d" % it
-        assert np.max(np.abs(rew_h - o_rew)) <= TOL
-        assert np.array_equal(k_time, tt), "time markers differ at step %d" % it
-        assert np.array_equal(env.done_mask().cpu().numpy(), (o_term != 0).astype(np.uint8))
-        reseeded = t0 == -1 - ((tick - 1) & 1)
-        assert np.array_equal(k_state[:, reseeded], st[:, reseeded])          # float32 reset specification, bit for bit
-        assert np.all(rew_h[reseeded] == 0) and np.all(term_h[reseeded] == 0)
-        live = ~reseeded
-        if live.any():
-            assert np.max(np.abs(k_state[0:2, live] - st[0:2, live])) <= TOL
-            assert np.max(angle_diff(k_state[2, live], st[2, live])) <= TOL
-            assert np.max(np.abs(k_state[5:7, live] - st[5:7, live])) <= 1e-7
-            assert np.array_equal(k_state[3:5, live], st[3:5, live])
-        finished += int((o_term != 0).sum())
-        restarted += int(reseeded.sum())
-    return finished, restarted
 
 
 @pytest.mark.parametrize("n,steps,continuous", [(262144, 10, False), (262144, 10, True), (1 << 19, 4, False)],
@@ -656,33 +566,10 @@ def test_per_world_tables_match_the_oracle(torch, oracle, continuous):
     assert finished > n // 20
 
 
-def _oracle_next_step_tables(oracle, st, tt, act, tables, seed, tick, env_offset):
-    """one tick of the next-step restart convention on the CPU, from the oracle's own primitives (step_tables and the
-    masked reset_tables): what step_tables_ns_kernel must reproduce.  st float32 [7][n], tt int32 [n] in place;
-    returns (reward, term)."""
-    n = tt.shape[0]
-    fresh, finished = -3 - ((tick - 1) & 1), -1 - ((tick - 1) & 1)
-    tt[tt == fresh] = 0
-    restart = tt == finished
-    pending = tt < 0
-    s64 = np.ascontiguousarray(st.astype(np.float64))
-    t = np.ascontiguousarray(np.where(pending, 0, tt).astype(np.int32))
-    rew, term, _ = oracle.step_tables(s64, t, act, tables, waves=1, seed=seed, tick=tick, env_offset=env_offset)
-    live = ~pending
-    st[:, live] = s64[:, live].astype(np.float32)
-    tt[live] = np.where(term[live] != 0, -1 - (tick & 1), t[live])
-    rew = np.where(live, rew, 0.0).astype(np.float32)
-    term = np.where(live, term, 0).astype(np.uint8)
-    if restart.any():
-        oracle.reset_tables(st, tt, tables, waves=1, seed=seed, tick=tick, env_offset=env_offset, mask=restart)
-        tt[restart] = -3 - (tick & 1)
-    return rew, term
-
-
 @pytest.mark.parametrize("continuous", [False, True])
 def test_per_world_tables_next_step_restart_matches_the_oracle(torch, oracle, continuous):
-    """auto_reset='next_step' with one obstacle list per world (role-split launch, re-seeding eight lanes per world against the
-    world's own table): every tick against the oracle -- termination codes, markers in the time row and the re-seeded
+    """auto_reset='next_step' with one obstacle list per world (six rows: the restart inside the stepping tile, the rows handed
+    over through LDS to the re-seeding lanes): every tick against the oracle -- termination codes, markers in the time row and the re-seeded
     states bit for bit, floats of the stepped worlds within 1e-5 (teacher-forced: the oracle restarts every tick from the
     kernel's state)."""
     n, K = 40000 + 3, 6
@@ -1267,17 +1154,6 @@ def test_obs_is_a_view_and_invariants_at_full_size(torch):
 # ------------------------------------------------------------------------------------------------
 # on-device bearing policy (main/testing/test_optimal.py:8-28)
 # ------------------------------------------------------------------------------------------------
-def _bearing_np(s):
-    """the reference's policy in float64 on a [7][n] state; also returns the distance to its decision threshold"""
-    two_pi = 2 * np.pi
-    boat = (s[2] + np.pi / 2 + two_pi) % two_pi
-    goal = (np.arctan2(s[4] - s[1], s[3] - s[0]) + two_pi) % two_pi
-    diff = goal - boat
-    act = np.where(np.abs(diff) > 8 / 180 * np.pi, np.where(diff > 0, 0, 1), 2)
-    edge = np.minimum(np.abs(np.abs(diff) - 8 / 180 * np.pi), np.abs(diff) + (np.abs(diff) <= 8 / 180 * np.pi) * 10)
-    return act.astype(np.uint8), edge
-
-
 @pytest.mark.parametrize("mode", [0, 2], ids=["no_reset", "next_step"])
 def test_bearing_policy_steps_match_oracle(torch, oracle, mode):
     from aquaticgymenv_amd import presets

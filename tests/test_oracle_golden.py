@@ -191,6 +191,48 @@ def test_discrete_action_index_wraps_like_a_python_list(oracle):
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[2], outs[3])
 
 
+def test_out_of_range_discrete_actions_clamp_in_64_bits(oracle):
+    """an int64 index beyond 32 bits is clamped as a whole (2^32 + 1 -> 2, -2^32 + 1 -> 0), not truncated to int32 first
+    (which would read 1 and 1): the value tests/test_dispatch_matrix.py feeds the kernels"""
+    s0 = np.array([[40.0], [60.0], [1.0], [70.0], [20.0], [0.0], [0.0]])
+    outs = {}
+    for a in (0, 1, 2, 2 ** 32 + 1, -2 ** 32 + 1, 2 ** 32, 2 ** 63 - 1, -2 ** 63, 255, -4):
+        s = s0.copy()
+        oracle.step(s, np.zeros(1, dtype=np.int32), np.array([a], dtype=np.int64), waves=0, noise_u=np.zeros((2, 1)))
+        outs[a] = s[:, 0].copy()
+    for a, want in ((2 ** 32 + 1, 2), (-2 ** 32 + 1, 0), (2 ** 32, 2), (2 ** 63 - 1, 2), (-2 ** 63, 0), (255, 2), (-4, 0)):
+        assert np.array_equal(outs[a], outs[want]), a
+    assert not np.array_equal(outs[1], outs[2])
+
+
+@pytest.mark.parametrize("continuous", [False, True])
+@pytest.mark.parametrize("env_offset", [0, 7, 2 ** 32 - 3])
+def test_exported_sampled_actions_are_the_ones_the_rollout_draws(oracle, continuous, env_offset):
+    """sample_actions() (the Philox stream-4 actions, exported) fed back as stored actions reproduces the oracle's own
+    sampled rollout bit for bit -- in every restart mode, over steps that finish and restart worlds"""
+    from aquaticgymenv_amd import presets
+    n = 3011
+    for mode in (0, 1, 2):
+        st = np.zeros((7, n), dtype=np.float32)
+        tt = np.zeros(n, dtype=np.int32)
+        oracle.reset(st, tt, obstacles=presets.BENCH8, seed=5, tick=1 << 40, env_offset=env_offset)
+        tt[:] = np.random.RandomState(1).randint(990, 1001, n)
+        a, b = (st.copy(), tt.copy()), (st.copy(), tt.copy())
+        for tick in range(4):
+            _, r1, t1, _ = oracle.rollout_f32(a[0], a[1], 1, obstacles=presets.BENCH8, continuous=continuous, seed=5,
+                                              tick0=tick, env_offset=env_offset, auto_reset=mode)
+            act = oracle.sample_actions(n, continuous, seed=5, tick=tick, env_offset=env_offset)
+            assert act.dtype == (np.float32 if continuous else np.uint8) and act.shape == ((2, n) if continuous else (n,))
+            _, r2, t2, _ = oracle.rollout_f32(b[0], b[1], 1, obstacles=presets.BENCH8, actions=act, seed=5, tick0=tick,
+                                              env_offset=env_offset, auto_reset=mode)
+            assert np.array_equal(r1, r2) and np.array_equal(t1, t2)
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        if continuous:
+            assert act.min() >= 0.2 and act.max() <= 0.5
+        else:
+            assert set(np.unique(act)) == {0, 1, 2}
+
+
 @pytest.mark.parametrize("n", [1, 63, 4099])
 def test_every_entry_point_of_the_c_oracle_at_ragged_sizes(oracle, n):
     """every exported function of oracle/aqua_oracle.c at sizes that are not multiples of anything, with the buffers sized
