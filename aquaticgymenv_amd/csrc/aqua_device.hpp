@@ -23,6 +23,9 @@ constexpr float BAND = 1.0e-4f;          // half-width of the knife-edge band of
 // two more roundings at magnitude 5 and a hardware sqrt (bound 1.2e-6, largest seen 1.3e-7): it keeps 4e-6.
 constexpr float BAND_TIGHT = 2.0e-6f;
 constexpr float BAND_TIGHT_GOAL = 4.0e-6f;
+// ... of the heading's fold at +-pi: the float32 sum th + w is within 2e-7 of the reference's float64 one (its own
+// rounding at magnitude pi, 1.2e-7, and the float32 w: thrusts' difference times 0.4f against / 2.5 in float64).
+constexpr float WRAP_BAND = 1.0e-6f;
 constexpr int RESET_TRIES = 64;
 constexpr int MAX_OBST = 64;
 
@@ -32,8 +35,9 @@ constexpr int MAX_OBST = 64;
 struct ObstF {
     float cx, cy, hx, hy;       // box centre and half extents (aqua.py:381-384); circle: hx = hy = 0
     float r2;                   // R^2 with R = obstacle radius + 2.5 (circle) or 2.5 (rect)
-    float w;                    // band2_tight(R_max) / band2_tight(R): scales this obstacle's compensated margin so
-                                // that ONE threshold (the header's) gives every obstacle the band of its own radius
+    float w;                    // band2_tight(R_max) / band2_tight(R, e): scales this obstacle's compensated margin so
+                                // that ONE threshold (the header's) gives every obstacle the band of its own radius,
+                                // widened by e, the float32 rounding of its centre and half extents (tight_rounded)
     float pad[2];
 };
 static_assert(sizeof(ObstF) == 32, "ObstF is two float4");
@@ -214,8 +218,10 @@ __device__ __forceinline__ void sincos_bounded(float a, float& s, float& c)
     c = __builtin_amdgcn_cosf(rev);
 }
 
-// theta <- theta + w folded into [-pi, pi) (aqua.py:128-133).  The float32 neighbours of +-pi are
-// classified exactly as the float64 reference classifies them.
+// theta <- theta + w folded into [-pi, pi) (aqua.py:128-133), decided on the ROUNDED float32 sum th + w.  The reference
+// decides on the float64 sum with its float64 w, so within a few 1e-7 of +-pi the two may fold to opposite ends (a heading
+// of -pi + e where the reference has pi - e: 2 pi apart).  fast_step therefore hands every world whose sum lies within
+// WRAP_BAND of +-pi to the float64 path, which folds the reference's own sum.
 __device__ __forceinline__ float wrap_add(float th, float w)
 {
     constexpr float PI_F = 3.14159274101257324f;
@@ -545,6 +551,7 @@ __device__ __forceinline__ bool fast_step(EnvState& e, float h, float w, float c
     const float ddy = fmaf(chord, c, e.wy);
     const float xn = e.x + ddx, yn = e.y + ddy;
     const float thn = wrap_add(e.th, w);
+    const bool wrap_knife = fabsf(fabsf(e.th + w) - 3.14159274101257324f) < WRAP_BAND;   // (see wrap_add)
     // wave random walk (aqua.py:188-191): drawn after the move
     const float wxn = __builtin_amdgcn_fmed3f(fmaf(u0, k.sigma, e.wx), -k.W, k.W);
     const float wyn = __builtin_amdgcn_fmed3f(fmaf(u1, k.sigma, e.wy), -k.W, k.W);
@@ -622,9 +629,10 @@ __device__ __forceinline__ bool fast_step(EnvState& e, float h, float w, float c
         const float xlo = ddx - (xn - e.x), ylo = ddy - (yn - e.y);
         const float mb2 = fminf(fminf((xn - 2.5f) + xlo, (yn - 2.5f) + ylo), fminf((97.5f - xn) - xlo, (97.5f - yn) - ylo));
         float mo2 = 3.0e38f;
-        // Each margin is scaled by its obstacle's w >= 1 (sign unchanged): |d^2 - R^2| < band2_tight(R_max) / w is the
-        // band of THAT obstacle's radius, 2.5 (R + BAND) BAND_TIGHT + 4 ulp(R^2) -- not R_max's, which for the
-        // R = 2.5 of every rectangle would be several times wider than its own in distance.
+        // Each margin is scaled by its obstacle's w > 0 (sign unchanged): |d^2 - R^2| < band2_tight(R_max) / w is the
+        // band of THAT obstacle's radius, 2.5 (R + BAND) (BAND_TIGHT + e) + 4 ulp(R^2) -- not R_max's, which for the
+        // R = 2.5 of every rectangle would be several times wider than its own in distance; e is the distance by which
+        // the float32 copy of the obstacle's row may move its surface (0 for rows on the float32 grid).
         if constexpr (PER_WORLD) {
             // A cold path -- a wavefront in two hundred takes it -- but one that ENDS the launch: every wavefront of a
             // streaming launch reaches this point at about the same time, so the launch lasts as long as the slowest second
@@ -662,6 +670,7 @@ __device__ __forceinline__ bool fast_step(EnvState& e, float h, float w, float c
         if (knife) { mc_f = mb2; mo_f = mo2; mg_f = mg2; }
         knife = knife && ((fabsf(mb2) < BAND_TIGHT) || (fabsf(mg2) < BAND_TIGHT_GOAL) || (fabsf(mo2) < k.band2_tight));
     }
+    knife = knife || wrap_knife;                           // the heading is folded by the float64 path (~3e-7 of world-steps)
     term = (fminf(mc_f, mo_f) < 0.0f) ? 1u : (tn > k.time_limit ? 2u : (mg_f <= 0.0f ? 3u : 0u));   // aqua.py:200-211
     reward = term == 0u ? shaped : (term == 3u ? 10.0f : -10.0f);
     e.x = xn; e.y = yn; e.th = thn; e.wx = wxn; e.wy = wyn; e.t = tn;

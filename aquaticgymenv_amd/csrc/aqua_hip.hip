@@ -2379,6 +2379,21 @@ size_t aqua_obstacle_blob_bytes(int K)
     return used < AQUA_BLOB_MIN_BYTES ? AQUA_BLOB_MIN_BYTES : used;     // the kernels touch the first five 64-byte lines
 }
 
+// The second look's band of one obstacle, 2.5 (R + BAND) BAND_TIGHT + 4 ulp(R^2) (fast_step), widened by how far the float32
+// copy of the obstacle's row lies from the reference's float64 row: the first and second looks measure the distance to the
+// rounded box, and a centre near 70 rounds by up to 3.8e-6 -- more than BAND_TIGHT.  (Rows on a float32 grid: no change.)
+static double tight_rounded(double R, double rounding)
+{
+    return 2.5 * (R + static_cast<double>(BAND)) * (static_cast<double>(BAND_TIGHT) + rounding) + 4.0 * 1.1920929e-7 * R * R;
+}
+// bound on the distance error of a row (cx, cy, kind, a, b) held as float32 centre and half extents
+static double geometry_rounding(const double* o)
+{
+    const auto e = [](double v) { return std::fabs(static_cast<double>(static_cast<float>(v)) - v); };
+    const double hx = o[2] == 0.0 ? 0.0 : o[3] / 2, hy = o[2] == 0.0 ? 0.0 : o[4] / 2;
+    return e(o[0]) + e(o[1]) + e(hx) + e(hy);
+}
+
 int aqua_pack_obstacles(const double* rows, int K, void* blob_host, size_t blob_bytes)
 {
     if (K < 0 || K > AQUA_MAX_OBSTACLES) return fail(AQUA_E_INVALID, "K=%d outside [0, %d]", K, AQUA_MAX_OBSTACLES);
@@ -2419,7 +2434,8 @@ int aqua_pack_obstacles(const double* rows, int K, void* blob_host, size_t blob_
     };
     h->band2_tight = static_cast<float>(tight(r_max));
     for (int k = 0; k < K; ++k)                          // per-obstacle scale of the compensated margin (ObstF::w)
-        f[k].w = static_cast<float>(static_cast<double>(h->band2_tight) / tight(std::sqrt(static_cast<double>(f[k].r2))));
+        f[k].w = static_cast<float>(static_cast<double>(h->band2_tight) /
+                                    tight_rounded(std::sqrt(static_cast<double>(f[k].r2)), geometry_rounding(d + 5 * k)));
     if (K <= QUICK_MAX) {                                // quick table: the first look's operands, four obstacles per group
         float* q = reinterpret_cast<float*>(static_cast<char*>(blob_host) + quick_offset(K));
         const auto group = [&](int vec0, int j) { return q + 4 * vec0 + (j & 3); };      // + 4 * field
@@ -2618,7 +2634,8 @@ int aqua_pack_tables(const double* rows, int K, int64_t N, int64_t tld, float* t
             f[2 * tld] = static_cast<float>(hx); f[3 * tld] = static_cast<float>(hy);
             const float r2 = static_cast<float>(R * R);
             f[4 * tld] = r2;
-            f[5 * tld] = static_cast<float>(static_cast<double>(b_max) / tight(std::sqrt(static_cast<double>(r2))));
+            f[5 * tld] = static_cast<float>(static_cast<double>(b_max) /
+                                            tight_rounded(std::sqrt(static_cast<double>(r2)), geometry_rounding(o)));
         }
     // the world-major copy behind the struct of arrays: [tld][K][6], a world's table contiguous (tables_world_major())
     float* const aos = tab32_host + static_cast<size_t>(6) * K * tld;

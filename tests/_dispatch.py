@@ -70,9 +70,13 @@ def _split_top(s):
     return out + [cur]
 
 
-def read_thresholds(paths=SOURCES):
+_FLOAT = re.compile(r"\s*([-+]?(?:\d+\.\d*|\.\d+|\d+)(?:[eE][-+]?\d+)?)[fF]?\s*$")
+
+
+def read_thresholds(paths=SOURCES, floats=False):
     """every integer `#define NAME value` and namespace-level `constexpr <type> NAME = value[, NAME = value];` of the
-    sources, in order (later definitions may use earlier ones)"""
+    sources, in order (later definitions may use earlier ones); with `floats`, also the `constexpr float|double` ones
+    whose value is a plain literal (1.0e-4f -> 1e-4, the literal's value in double, not rounded to float)"""
     names = {}
     for path in paths:
         with open(path) as f:
@@ -86,11 +90,15 @@ def read_thresholds(paths=SOURCES):
                 if v is not None:
                     names[m.group(1)] = v
                 continue
-            m = re.match(r"\s*(?:static\s+)?constexpr\s+[\w:]+\s+(.*?);", line)
+            m = re.match(r"\s*(?:static\s+)?constexpr\s+([\w:]+)\s+(.*?);", line)
             if m:
-                for decl in _split_top(m.group(1)):
+                real = m.group(1) in ("float", "double")
+                for decl in _split_top(m.group(2)):
                     d = re.match(r"\s*([A-Za-z_]\w*)\s*=\s*(.+)$", decl)
-                    if d:
+                    f = _FLOAT.match(d.group(2)) if d and real and floats else None
+                    if f:
+                        names.setdefault(d.group(1), float(f.group(1)))
+                    elif d:
                         v = _eval(d.group(2), names)
                         if v is not None:
                             names.setdefault(d.group(1), v)
