@@ -1,0 +1,73 @@
+"""ctypes binding of libaqua_policy.so (include/aqua_policy.h).  No fallback: if the HIP library is missing or does
+not load, importing this module raises -- the Q-network has no CPU path."""
+import ctypes
+import os
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("AQUA_POLICY_LIB") or os.path.join(_HERE, "lib", "libaqua_policy.so")
+
+ABI_VERSION = 1
+E_INVALID, E_ALIGN, E_NODEVICE = -1, -2, -3
+SHAPES = (5, 64, 64, 3)           # main/impl/dqn.py:301-314
+STREAM = 5                        # Philox stream of the epsilon-greedy draws
+
+# every symbol include/aqua_policy.h declares (tests/test_qpolicy_cpu.py checks the library exports them all)
+SYMBOLS = ("aquapol_version", "aquapol_last_error", "aquapol_weights_bytes", "aquapol_pack_weights", "aquapol_act_f32")
+
+
+class AquaPolicyError(RuntimeError):
+    pass
+
+
+def _load():
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(
+            "libaqua_policy.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
+            "`python -m aquaticgymenv_amd.build` (needs hipcc); there is no CPU fallback")
+    # torch's libamdhip64 first, so that this library's NEEDED entry resolves to the same runtime (see _capi.py)
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(LIB_PATH)
+    vp, i64, u64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_float
+    lib.aquapol_version.restype = ci
+    lib.aquapol_last_error.restype = ctypes.c_char_p
+    lib.aquapol_weights_bytes.restype = ctypes.c_size_t
+    lib.aquapol_pack_weights.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci), vp, ctypes.c_size_t]
+    lib.aquapol_pack_weights.restype = ci
+    lib.aquapol_act_f32.argtypes = [vp, vp, i64, ci, i64, i64, cf, u64, u64, vp, vp, vp, i64, vp, vp]
+    lib.aquapol_act_f32.restype = ci
+    if lib.aquapol_version() != ABI_VERSION:
+        raise ImportError("libaqua_policy.so ABI %d != binding %d: rebuild" % (lib.aquapol_version(), ABI_VERSION))
+    return lib
+
+
+lib = _load()
+
+
+def check(rc, what):
+    if rc != 0:
+        msg = lib.aquapol_last_error().decode("utf-8", "replace")
+        if rc == E_INVALID:
+            raise ValueError("%s: %s" % (what, msg))
+        raise AquaPolicyError("%s failed (code %d): %s" % (what, rc, msg))
+
+
+def pack_weights(layers):
+    """layers: [(kernel [in, out], bias [out])] * 3 as tf_import.dense_stack() returns them -> numpy uint8 array holding
+    the device-format blob.  Another architecture than 5-64-64-3: ValueError."""
+    import numpy as np
+    layers = list(layers)
+    if len(layers) != 3:
+        raise ValueError("the Q-network has three dense layers, got %d" % len(layers))
+    ks = [np.ascontiguousarray(k, dtype=np.float32) for k, _ in layers]
+    bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for _, b in layers]
+    for k, b in zip(ks, bs):
+        if k.ndim != 2 or b.shape[0] != k.shape[1]:
+            raise ValueError("kernel %s / bias %s: expected [in, out] and [out]" % (k.shape, b.shape))
+    if ks[1].shape[0] != ks[0].shape[1] or ks[2].shape[0] != ks[1].shape[1]:
+        raise ValueError("layer widths do not chain: %s" % ([k.shape for k in ks],))
+    shapes = (ctypes.c_int * 4)(ks[0].shape[0], ks[0].shape[1], ks[1].shape[1], ks[2].shape[1])
+    n = lib.aquapol_weights_bytes()
+    blob = np.zeros(n, dtype=np.uint8)
+    check(lib.aquapol_pack_weights(ks[0].ctypes.data, bs[0].ctypes.data, ks[1].ctypes.data, bs[1].ctypes.data,
+                                   ks[2].ctypes.data, bs[2].ctypes.data, shapes, blob.ctypes.data, n), "aquapol_pack_weights")
+    return blob

@@ -234,6 +234,7 @@ class BatchedAqua(object):
                                           # that a reset between two steps does not shift the steps' tick parity
                                           # (the next-step restart markers carry it, include/aqua_hip.h)
         self._action_soa = None           # staging for (N, 2) -> [2][ld] continuous actions
+        self._policy_action = None        # uint8 [ld]: where a QNetwork policy writes the actions of the step about to be taken
 
     # ------------------------------------------------------------------ plumbing
     def _stream(self):
@@ -358,12 +359,116 @@ class BatchedAqua(object):
             return _capi.ACT_BEARING
         raise ValueError("unknown on-device policy %r (use 'random' or 'bearing')" % (name,))
 
-    def step(self, action=None, soa=False, noise=None, sample_actions=False, policy=None):
+    # -- a Q-network as the on-device policy (aquaticgymenv_amd/qpolicy.py, include/aqua_policy.h)
+    @property
+    def policy_action(self):
+        """uint8 [ld]: the actions a QNetwork policy chose for the last step(policy=qnet) / replay of capture_policy_step()
+        (what ReplayRing.before_step() records)."""
+        if self._policy_action is None:
+            self._policy_action = self.torch.zeros(self.ld, dtype=self.torch.uint8, device=self.device)
+        return self._policy_action
+
+    @staticmethod
+    def _is_network(policy):
+        return getattr(policy, "_aquapol_network", False) is True
+
+    def _check_network(self, qnet):
+        if self.continuous:
+            raise ValueError("the Q-network policy (main/impl/dqn.py) is defined for discrete actions")
+        if qnet.device != self.device:
+            raise ValueError("the environment is on %s, the network on %s" % (self.device, qnet.device))
+
+    def _policy_launch(self, qnet, epsilon, tick, tick_base, s):
+        """the network's actions for the step with this tick into policy_action, from the state rows -> return code"""
+        return qnet.launch(self.state.data_ptr(), self.ld, False, self.num_envs, self.env_offset, epsilon, self.seed, tick,
+                           tick_base, self.policy_action.data_ptr(), None, 0, None, s)
+
+    def _step_launch(self, aptr, kind, ald, tick, tick_base, reward_ptr, term_ptr, done_ptr, s):
+        """one step launch with explicit output pointers -> return code"""
+        lib = _capi.lib
+        if self.per_world:
+            return lib.aqua_step_tables_f32(ctypes.byref(self.params), self._tab32.data_ptr(), self._tab64.data_ptr(), self.K,
+                                            self.ld, self._r_max, self.num_envs, self.env_offset, self.state.data_ptr(), self.ld,
+                                            self.time.data_ptr(), aptr, kind, ald, None, 0, self.seed, tick, tick_base,
+                                            reward_ptr, term_ptr, done_ptr, self._norm_ptr(), int(self.auto_reset), s)
+        return lib.aqua_step_f32(ctypes.byref(self.params), self._blob_ptr(), self.K, self.num_envs, self.env_offset,
+                                 self.state.data_ptr(), self.ld, self.time.data_ptr(), aptr, kind, ald, None, 0, self.seed, tick,
+                                 tick_base, reward_ptr, term_ptr, done_ptr, self._norm_ptr(), int(self.auto_reset), s)
+
+    def _network_step(self, qnet, epsilon, reward_ptr, term_ptr, done_ptr):
+        """policy launch + step launch on the current stream, both keyed by the tick of the step"""
+        from . import _policy_capi
+        with self.torch.cuda.device(self.device):
+            s = self._stream()
+            _policy_capi.check(self._policy_launch(qnet, epsilon, self._tick, None, s), "aquapol_act_f32")
+            _capi.check(self._step_launch(self.policy_action.data_ptr(), _capi.ACT_U8, 0, self._tick, None, reward_ptr, term_ptr,
+                                          done_ptr, s), "aqua_step_f32")
+        self._tick += 1
+
+    def _network_rollout(self, qnet, epsilon, steps, keep_all, done_history):
+        self._check_network(qnet)
+        reward, term, ostride = self._rollout_out(steps, keep_all)
+        done, dstride = self._done_out(steps, done_history)
+        for t in range(steps):
+            self._network_step(qnet, epsilon, reward.data_ptr() + 4 * t * ostride, term.data_ptr() + t * ostride,
+                               done.data_ptr() + 8 * t * dstride)
+        return reward, term
+
+    def capture_policy_step(self, qnet, epsilon=0.0):
+        """One step under a QNetwork policy captured into a HIP graph: every launch() of the returned RolloutGraph is
+        policy kernel -> step -> tick advance.  The policy reads the device tick base before the advance and draws with the
+        tick the step is about to use, so every replay explores afresh; the actions of the last replay are in
+        policy_action; qnet.load() between replays changes the weights the graph acts with."""
+        from . import _policy_capi
+        torch, lib = self.torch, _capi.lib
+        if not self._is_network(qnet):
+            raise ValueError("capture_policy_step(): expected a QNetwork")
+        self._check_network(qnet)
+        self.policy_action                                    # (allocated before the capture begins)
+        self._sync_device_tick()
+        cap = torch.cuda.Stream(device=self.device)
+        cap.wait_stream(torch.cuda.current_stream(self.device))
+        handle = ctypes.c_void_p()
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(cap):
+                s = self._stream()
+                _capi.check(lib.aqua_graph_begin(s), "aqua_graph_begin")
+                rc_pol = rc = 0
+                try:
+                    tb = self._tick_dev.data_ptr()
+                    rc_pol = self._policy_launch(qnet, epsilon, 0, tb, s)
+                    if rc_pol == 0:
+                        rc = self._step_launch(self.policy_action.data_ptr(), _capi.ACT_U8, 0, 0, tb, self.reward.data_ptr(),
+                                               self.term.data_ptr(), self.done_bits.data_ptr(), s)
+                    if rc_pol == 0 and rc == 0:
+                        rc = lib.aqua_tick_advance(tb, 1, s)
+                finally:
+                    rc_end = lib.aqua_graph_end(s, ctypes.byref(handle))
+                if (rc_pol != 0 or rc != 0) and rc_end == 0:
+                    lib.aqua_graph_destroy(handle)
+                _policy_capi.check(rc_pol, "capture policy")
+                _capi.check(rc, "capture step")
+                _capi.check(rc_end, "aqua_graph_end")
+        finally:
+            torch.cuda.current_stream(self.device).wait_stream(cap)
+        g = RolloutGraph(self, handle, 1, self.reward, self.term)
+        g._actions = (qnet, self.policy_action)
+        g.done_history = None
+        return g
+
+    def step(self, action=None, soa=False, noise=None, sample_actions=False, policy=None, epsilon=0.0):
         """One batched step (aqua.py:135-213).  Returns (obs view [N,5], reward [N], term [N] uint8).
         noise: optional float32 [2][>=N] uniforms in [-1, 1) replacing the Philox draws (parity tests).
-        policy: 'random' (== sample_actions) or 'bearing': the action is produced on the device."""
+        policy: 'random' (== sample_actions) or 'bearing': the action is produced on the device;
+                a QNetwork: its (epsilon-)greedy action, one policy launch ahead of the step launch (policy_action holds it)."""
         torch = self.torch
         n = self.num_envs
+        if self._is_network(policy):
+            if noise is not None:
+                raise ValueError("step(policy=<QNetwork>): injected noise is for the parity tests of the step kernels")
+            self._check_network(policy)
+            self._network_step(policy, epsilon, self.reward.data_ptr(), self.term.data_ptr(), self.done_bits.data_ptr())
+            return self.obs, self.reward[:n], self.term[:n]
         if sample_actions or policy is not None:
             keep, aptr, kind, ald = None, None, self._device_policy(policy or "random"), 0
         else:
@@ -503,7 +608,7 @@ class BatchedAqua(object):
             raise ValueError("done_history must be int64 [T][>= ld/64]")
         return done_history, done_history.stride(0)
 
-    def rollout(self, steps, actions=None, fused=False, keep_all=True, done_history=None, events=None):
+    def rollout(self, steps, actions=None, fused=False, keep_all=True, done_history=None, events=None, epsilon=0.0):
         """`steps` consecutive batched steps queued from C without returning to Python.
         events: a LaunchEvents (or a (start, stop) pair of which either may be None) stamped by the first launch's start and
                 the last launch's end (one launch per step, one obstacle table for the batch only).
@@ -511,8 +616,13 @@ class BatchedAqua(object):
                  of main/testing/test_optimal.py evaluated on the device;
                  discrete: uint8/int32/int64 [T][>=N]; continuous: float32 [T][2][>=N].
         fused=True runs them as ONE launch with the state held in registers.
+                 a QNetwork: its (epsilon-)greedy actions, a policy launch and a step launch per step (not with fused=True).
         Returns (reward, term): [T][ld] tensors when keep_all, else the last step's [ld] buffers."""
         torch = self.torch
+        if self._is_network(actions):
+            if fused or events is not None:
+                raise ValueError("rollout(actions=<QNetwork>): one policy launch and one step launch per step (no fused, no events)")
+            return self._network_rollout(actions, epsilon, steps, keep_all, done_history)
         aptr, kind, ald, astride = self._rollout_args(steps, actions, self.ld)
         reward, term, ostride = self._rollout_out(steps, keep_all)
         done, dstride = self._done_out(steps, done_history)

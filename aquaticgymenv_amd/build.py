@@ -21,6 +21,14 @@ ARCH = "gfx950"
 # tag of bench.py and profiles/traffic.json) depends on the sources and this command line only.
 COMMON_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-std=c++17", "-shared", "-fPIC", "-fno-honor-nans", "-cuid=aqua_hip"]
 
+# libaqua_policy.so (include/aqua_policy.h): the Q-network kernel, a translation unit and a library of its own -- the
+# command line and the hash of libaqua_hip.so do not depend on it.  Same flags, its own compilation-unit id.
+POLICY_SRC = [os.path.join(HERE, "csrc", "aqua_policy.hip")]
+POLICY_DEPS = POLICY_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
+                            os.path.join(os.path.dirname(HERE), "include", "aqua_policy.h")]
+POLICY_LIB = os.path.join(HERE, "lib", "libaqua_policy.so")
+POLICY_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_policy"]
+
 
 def hipcc_path():
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
@@ -47,6 +55,26 @@ def build_hip(force=False, verbose=False, extra_flags=()):
     subprocess.check_call(cmd)
     os.replace(LIB + ".tmp", LIB)
     return LIB
+
+
+def policy_needs_build():
+    if not os.path.exists(POLICY_LIB):
+        return True
+    t = os.path.getmtime(POLICY_LIB)
+    return any(os.path.getmtime(d) > t for d in POLICY_DEPS)
+
+
+def build_policy(force=False, verbose=False, extra_flags=()):
+    """Compile csrc/aqua_policy.hip -> lib/libaqua_policy.so for gfx950 (a few seconds).  Returns the library path."""
+    if not force and not policy_needs_build():
+        return POLICY_LIB
+    os.makedirs(os.path.dirname(POLICY_LIB), exist_ok=True)
+    cmd = [hipcc_path(), *POLICY_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", POLICY_LIB + ".tmp", *POLICY_SRC]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(POLICY_LIB + ".tmp", POLICY_LIB)
+    return POLICY_LIB
 
 
 def build_variant(name, flags, verbose=False):
@@ -97,3 +125,4 @@ if __name__ == "__main__":
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
     print(build_hip(force="--force" in sys.argv, verbose=True))
+    print(build_policy(force="--force" in sys.argv, verbose=True))

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Replay one of the reference's trained DQN policies (5-64-64-3 MLP, weights committed as a test fixture, read from
-the reference's SavedModel without TensorFlow by aquaticgymenv_amd.tf_import) on a batch of worlds, recording the
+the reference's SavedModel without TensorFlow by aquaticgymenv_amd.tf_import, evaluated by aquaticgymenv_amd.qpolicy.QNetwork
+-- tf_import.GreedyQPolicy is the same network as torch GEMMs) on a batch of worlds, recording the
 transitions into the device-side experience ring the way main/impl/dqn.py:174 appends them to its deque.
 
     python examples/dqn_replay.py [--envs 16384] [--obstacles]
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 from aquaticgymenv_amd.batched import BatchedAqua
 from aquaticgymenv_amd.replay import ReplayRing
-from aquaticgymenv_amd.tf_import import GreedyQPolicy
+from aquaticgymenv_amd.qpolicy import QNetwork
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=16384)
@@ -24,15 +25,15 @@ args = ap.parse_args()
 
 z = np.load(os.path.join(ROOT, "tests", "golden", "dqn_policies.npz"))
 tag = "with_obs" if args.obstacles else "no_obs"
-policy = GreedyQPolicy([(z["%s_kernel%d" % (tag, i)], z["%s_bias%d" % (tag, i)]) for i in range(3)], "cuda")
+qnet = QNetwork([(z["%s_kernel%d" % (tag, i)], z["%s_bias%d" % (tag, i)]) for i in range(3)], "cuda")
 
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=2, auto_reset="next_step", normalized_obs=True)
 env.reset()
 ring = ReplayRing(env, capacity=64 * args.envs)
 episodes = success = 0
 for step in range(500):
-    action = policy(env.obs_norm).to(torch.uint8)          # argmax_a Q(s, a): three small GEMMs
-    ring.before_step(action)
+    action = qnet.act(env, out=env.policy_action)          # argmax_a Q(s, a): one launch of our own kernel (epsilon=... explores)
+    ring.before_step(env.policy_action)
     obs, reward, term = env.step(action)
     ring.after_step()
     episodes += int((term != 0).sum())
@@ -42,5 +43,7 @@ for step in range(500):
 print("%d episodes finished, %.1f %% reached the goal (published, one episode per run: %.1f %%)" %
       (episodes, 100.0 * success / max(episodes, 1), 100.0 * float(z["%s_published_success" % tag].mean())))
 s, a, r, s2, done = ring.sample(256)
+q_next = qnet.q_values(ring.s2, ring.size)                 # Q(s', .) of the whole ring for TD targets (dqn.py:262-292): [3][size]
 print("ring holds %d transitions; a sampled minibatch: s %s a %s r %s s' %s done %s" %
       (ring.size, tuple(s.shape), tuple(a.shape), tuple(r.shape), tuple(s2.shape), tuple(done.shape)))
+print("max_a Q(s', a) over the ring: mean %.3f" % float(q_next.max(dim=0).values.mean()))
