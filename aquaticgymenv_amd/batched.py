@@ -263,6 +263,13 @@ class BatchedAqua(object):
     def _norm_ptr(self):
         return self.obs_norm_buf.data_ptr() if self.obs_norm_buf is not None else None
 
+    def _refresh_norm(self, s):
+        """obs_norm from the state rows as they are on stream s, for the paths whose kernels have no epilogue of their own
+        (the fused rollouts, set_state()) -> return code"""
+        if self.obs_norm_buf is None:
+            return 0
+        return _capi.lib.aqua_obs_norm_f32(self.state.data_ptr(), self.ld, self.num_envs, None, self._norm_ptr(), s)
+
     @property
     def wave(self):
         return self.state[5:7, :self.num_envs].t()
@@ -651,6 +658,8 @@ class BatchedAqua(object):
                                                         dstride, self._norm_ptr(), int(self.auto_reset), 0, ev0, ev1,
                                                         self._stream()),
                             "aqua_rollout_events_f32")
+            if fused:                                 # the fused kernels keep the state in registers and write no obs_norm
+                _capi.check(self._refresh_norm(self._stream()), "aqua_obs_norm_f32")
         self._tick += steps
         return reward, term
 
@@ -691,7 +700,8 @@ class BatchedAqua(object):
     def capture_rollout(self, steps, actions=None, fused=False, keep_all=False, done_history=None, timing=False):
         """Capture `steps` batched steps into a HIP graph.  Noise stays fresh across replays: the
         kernels add a device-resident tick base that the graph's last node advances by `steps`.
-        timing=True: the graph starts and ends with an event-record node (RolloutGraph.elapsed_ms())."""
+        timing=True: the graph starts and ends with an event-record node (RolloutGraph.elapsed_ms()); with fused=True on a
+        batch with normalized_obs=True the interval includes the obs_norm refresh queued behind the fused launch."""
         torch = self.torch
         aptr, kind, ald, astride = self._rollout_args(steps, actions, self.ld, count=False)     # (nothing steps at capture time)
         reward, term, ostride = self._rollout_out(steps, keep_all)
@@ -749,6 +759,8 @@ class BatchedAqua(object):
                                               int(self.auto_reset), 1, s)        # advances the tick base itself
                 if rc == 0 and fused:
                     rc = lib.aqua_tick_advance(tb, steps, s)
+                if rc == 0 and fused:                 # a node of the graph: every replay leaves obs_norm current
+                    rc = self._refresh_norm(s)
             finally:
                 if timing:
                     rc_end = lib.aqua_graph_end_timed(s, ctypes.byref(handle), events[0], events[1])
@@ -863,3 +875,5 @@ class BatchedAqua(object):
         if time is not None:
             t = torch.as_tensor(np.asarray(time, dtype=np.int32)) if not isinstance(time, torch.Tensor) else time
             self.time[: self.num_envs].copy_(t.to(device=self.device, dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            _capi.check(self._refresh_norm(self._stream()), "aqua_obs_norm_f32")
