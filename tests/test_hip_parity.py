@@ -866,6 +866,15 @@ def test_reset_fixed_pose_and_distribution(torch):
         assert np.all((x >= 2.5) & (x <= 97.5) & (y >= 2.5) & (y <= 97.5) & (gx >= 2.5) & (gx <= 97.5))
         assert np.all(np.hypot(gx - x, gy - y) > 5.0 - 1e-4)
         assert np.all(np.abs(got[:, 5:7]) <= 0.05) and np.all(np.abs(got[:, 2]) <= np.float32(np.pi))
+        # ... the obstacle clauses among them (aqua.py:104,114): all five margins of tests/_placement.py, in float64 on
+        # the float32 placement; a world is exempt only where the trace of the specification says its loop was exhausted
+        from tests import _placement as P
+        traced, a_goal, a_boat = P.placement_trace(ci + 1, np.arange(200000, dtype=np.uint64), env.RESET_TICK_BASE, rows)
+        assert np.array_equal(traced.view(np.uint32), np.ascontiguousarray(got.T).view(np.uint32))
+        worst = P.check_acceptance(got.T, rows, a_goal, a_boat, "reset(), cfg %d" % ci)
+        print("cfg %d: worst acceptance margin goal %+.3g boat %+.3g" % ((ci,) + worst))
+        margins = P.acceptance_margins(got.T, rows)
+        assert np.all(margins[[1, 4]] >= P.MARGIN_BAR), "a goal or a boat was placed on an obstacle"
 
 
 # ------------------------------------------------------------------------------------------------

@@ -78,9 +78,11 @@ def test_option_cell_against_the_oracle(torch, oracle, cell):
     assert not failures, "\n".join(failures)
 
 
-def _run_chain(torch, oracle, fam, opts, noise, failures, inputs=None):
+def _run_chain(torch, oracle, fam, opts, noise, failures, inputs=None, observe=None):
     """inputs: (obstacles, state, time, actions) in place of the cell's own start -- a batch built for another purpose,
-    which then asserts its own conditions instead of the cells'"""
+    which then asserts its own conditions instead of the cells'.  observe(what, tick, state, time, reseeded): called with
+    the device's state after every step() of the chain and after the last step of every other entry point, once the
+    checks of this function have passed on it."""
     per_world = fam.table == "world"
     n, mode, off = fam.N, fam.mode, fam.env_offset
     continuous = fam.kind in D.CONTINUOUS
@@ -146,6 +148,8 @@ def _run_chain(torch, oracle, fam, opts, noise, failures, inputs=None):
         _check(what, safe, k_rew, k_term, o_rew, o_term, env.done_mask().cpu().numpy(), k_state, k_time, st, tt, reseeded,
                mode, tick)
         O.fixed_pose_conditions(opts, k_state, reseeded, never, what)
+        if observe is not None:
+            observe(what, tick, k_state, k_time, reseeded)
         if opts["waves"] == 0:
             assert np.all(k_state[5:7] == 0), "%s: waves=0 leaves a wave" % what
         if opts["norm"]:
@@ -162,13 +166,13 @@ def _run_chain(torch, oracle, fam, opts, noise, failures, inputs=None):
             continue
         try:
             _run_entry(torch, entry + tag, fresh, acts, policy, continuous, step_action, set_noise, noise_buf, n, want,
-                       st_last, mode, chain_state, chain_time, opts)
+                       st_last, mode, chain_state, chain_time, opts, observe)
         except AssertionError as e:
             failures.append(str(e))
 
 
 def _run_entry(torch, entry, fresh, acts, policy, continuous, step_action, set_noise, noise_buf, n, want, st_last, mode,
-               chain_state, chain_time, opts):
+               chain_state, chain_time, opts, observe=None):
     env = fresh()
     a = policy if policy is not None else acts
     done = None
@@ -251,6 +255,8 @@ def _run_entry(torch, entry, fresh, acts, policy, continuous, step_action, set_n
     _check("%s, final state" % entry, safe, rew[T - 1], term[T - 1], want[T - 1][0], want[T - 1][1], None, k_state, k_time,
            st, tt, reseeded, mode, tick)
     assert np.array_equal(k_state, chain_state) and np.array_equal(k_time, chain_time), "%s: final state differs from step()" % entry
+    if observe is not None:
+        observe("%s, final state" % entry, tick, k_state, k_time, reseeded)
     if opts["norm"]:
         _norm_failures(torch, env, entry)
 
