@@ -29,6 +29,13 @@ POLICY_DEPS = POLICY_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
 POLICY_LIB = os.path.join(HERE, "lib", "libaqua_policy.so")
 POLICY_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_policy"]
 
+# libaqua_learner.so (include/aqua_learner.h): the DQN update, again a translation unit and a library of its own.
+LEARNER_SRC = [os.path.join(HERE, "csrc", "aqua_learner.hip")]
+LEARNER_DEPS = LEARNER_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
+                              os.path.join(os.path.dirname(HERE), "include", "aqua_learner.h")]
+LEARNER_LIB = os.path.join(HERE, "lib", "libaqua_learner.so")
+LEARNER_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_learner"]
+
 
 def hipcc_path():
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
@@ -75,6 +82,26 @@ def build_policy(force=False, verbose=False, extra_flags=()):
     subprocess.check_call(cmd)
     os.replace(POLICY_LIB + ".tmp", POLICY_LIB)
     return POLICY_LIB
+
+
+def learner_needs_build():
+    if not os.path.exists(LEARNER_LIB):
+        return True
+    t = os.path.getmtime(LEARNER_LIB)
+    return any(os.path.getmtime(d) > t for d in LEARNER_DEPS)
+
+
+def build_learner(force=False, verbose=False, extra_flags=()):
+    """Compile csrc/aqua_learner.hip -> lib/libaqua_learner.so for gfx950.  Returns the library path."""
+    if not force and not learner_needs_build():
+        return LEARNER_LIB
+    os.makedirs(os.path.dirname(LEARNER_LIB), exist_ok=True)
+    cmd = [hipcc_path(), *LEARNER_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", LEARNER_LIB + ".tmp", *LEARNER_SRC]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(LEARNER_LIB + ".tmp", LEARNER_LIB)
+    return LEARNER_LIB
 
 
 def build_variant(name, flags, verbose=False):
@@ -126,3 +153,4 @@ if __name__ == "__main__":
             print(build_variant(name, flags, verbose=True))
     print(build_hip(force="--force" in sys.argv, verbose=True))
     print(build_policy(force="--force" in sys.argv, verbose=True))
+    print(build_learner(force="--force" in sys.argv, verbose=True))

@@ -46,6 +46,11 @@ class QNetwork(object):
         return self
 
     # ------------------------------------------------------------------ plumbing
+    @property
+    def blob(self):
+        """the device-format weights (uint8, aquapol_weights_bytes()): what DQNLearner re-packs into after every update"""
+        return self._blob
+
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 

@@ -1,0 +1,228 @@
+"""The DQN update of include/aqua_learner.h restated in numpy, for tests/test_learner_*.py: the reference the kernels are
+held to (float64), the yardstick (the same formulas in float32) and the exact integer form.
+
+Parameters are the canonical vector k0 [5][64], b0 [64], k1 [64][64], b1 [64], k2 [64][3], b2 [3].  A `ring` here is a
+dict of numpy arrays s [5][cap] f32, a [cap] u8, r [cap] f32, s2 [5][cap] f32, d [cap] u8, ok [cap] u8 and "size".
+"""
+import numpy as np
+
+from tests import _placement as P
+
+PARAMS = 4739
+SHAPES = ((5, 64), (64, 64), (64, 3))
+STRATEGIES = ("double_ref", "double", "fixed", "standard")
+STREAM = 6
+BETA1, BETA2, EPS = 0.9, 0.999, 1e-7
+
+
+def flatten(layers):
+    return np.concatenate([np.concatenate([np.asarray(k).reshape(-1), np.asarray(b).reshape(-1)]) for k, b in layers])
+
+
+def unflatten(theta):
+    out, at = [], 0
+    for i, o in SHAPES:
+        k = theta[at:at + i * o].reshape(i, o)
+        at += i * o
+        out.append((k, theta[at:at + o]))
+        at += o
+    assert at == PARAMS == theta.shape[0]
+    return out
+
+
+def forward(theta, x):
+    """x [B][5] -> (h1, h2 pre-activations [B][64], q [B][3]) in the dtype of theta and x"""
+    (k0, b0), (k1, b1), (k2, b2) = unflatten(theta)
+    h1 = x @ k0 + b0
+    h2 = np.maximum(h1, 0) @ k1 + b1
+    return h1, h2, np.maximum(h2, 0) @ k2 + b2
+
+
+def effective(idx, ring):
+    """the slot every sample uses: idx where 0 <= idx < size and ok[idx] != 0, else -1"""
+    idx = np.asarray(idx, dtype=np.int64)
+    inside = (idx >= 0) & (idx < ring["size"])
+    ok = np.zeros(idx.shape, dtype=bool)
+    ok[inside] = ring["ok"][idx[inside]] != 0
+    return np.where(ok, idx, -1).astype(np.int32)
+
+
+def drawn(seed, t_new, B, ring):
+    """the device draw of update t_new: int32 [B], -1 after four rejected attempts"""
+    size = int(ring["size"])
+    out = np.full(B, -1, dtype=np.int64)
+    for attempt in range(4):
+        r0 = P.draw(seed, np.arange(B), t_new, STREAM, attempt)[0]
+        cand = ((r0.astype(np.uint64) * np.uint64(size)) >> np.uint64(32)).astype(np.int64)
+        take = (out < 0) & (cand < size)
+        take[take] = ring["ok"][cand[take]] != 0
+        out[take] = cand[take]
+    return out.astype(np.int32)
+
+
+def batch_of(ring, eff, dtype):
+    """the valid samples of a minibatch: (x, a, r, x2, done)"""
+    sel = eff[eff >= 0].astype(np.int64)
+    return (ring["s"][:, sel].T.astype(dtype), ring["a"][sel].astype(np.int64), ring["r"][sel].astype(dtype),
+            ring["s2"][:, sel].T.astype(dtype), ring["d"][sel] != 0)
+
+
+def bootstrap(theta, theta_t, x, x2, strategy):
+    """-> (f [B], deciding Q-values [B][3] or None: the ones whose arg-max picks the target's action)"""
+    qt = forward(theta_t, x2)[2]
+    n = np.arange(x.shape[0])
+    if strategy == "double_ref":
+        dec = forward(theta, x)[2]
+        return qt[n, np.argmax(dec, axis=1)], dec
+    if strategy == "double":
+        dec = forward(theta, x2)[2]
+        return qt[n, np.argmax(dec, axis=1)], dec
+    if strategy == "fixed":
+        return qt.max(axis=1), None
+    assert strategy == "standard"
+    return forward(theta, x2)[2].max(axis=1), None
+
+
+def gradient(theta32, theta_t32, ring, eff, gamma, strategy, dtype):
+    """loss and gradient of the valid samples `eff` (effective()'s output), every operation in `dtype`:
+    -> dict(g [PARAMS], S (the unscaled sums), loss, n, delta, deciding)"""
+    theta, theta_t = theta32.astype(dtype), theta_t32.astype(dtype)
+    x, a, r, x2, done = batch_of(ring, eff, dtype)
+    n = x.shape[0]
+    if n == 0:
+        z = np.zeros(PARAMS, dtype=dtype)
+        return dict(g=z, S=z, loss=dtype(0), n=0, delta=np.zeros(0, dtype=dtype), deciding=None, done=done)
+    f, deciding = bootstrap(theta, theta_t, x, x2, strategy)
+    y = r + np.where(done, dtype(0), dtype(gamma) * f).astype(dtype)
+    h1, h2, q = forward(theta, x)
+    (k0, b0), (k1, b1), (k2, b2) = unflatten(theta)
+    delta = (q[np.arange(n), a] - y).astype(dtype)
+    dq = np.zeros((n, 3), dtype=dtype)
+    dq[np.arange(n), a] = delta
+    dh2 = (dq @ k2.T) * (h2 > 0)
+    dh1 = (dh2 @ k1.T) * (h1 > 0)
+    S = flatten([(x.T @ dh1, dh1.sum(axis=0)), (np.maximum(h1, 0).T @ dh2, dh2.sum(axis=0)), (np.maximum(h2, 0).T @ dq, dq.sum(axis=0))])
+    assert S.dtype == dtype and delta.dtype == dtype
+    g = S * dtype(2.0 / n)
+    loss = (delta * delta).sum(dtype=dtype) * dtype(1.0 / n)
+    return dict(g=g, S=S, loss=loss, n=n, delta=delta, deciding=deciding, done=done)
+
+
+def abs_sums(theta_i, theta_t_i, ring, eff, strategy):
+    """Integer networks and data: the largest sum of |terms| over every intermediate and every gradient element, in int64
+    (an upper bound of every partial sum in any order), and the exact unscaled gradient sums S."""
+    out = gradient(theta_i.astype(np.int64).astype(np.float64), theta_t_i.astype(np.float64), ring, eff, 1.0, strategy, np.float64)
+    x, a, r, x2, done = batch_of(ring, eff, np.int64)
+    n = x.shape[0]
+    worst = 0
+    for th, inp in ((theta_i, x), (theta_i, x2), (theta_t_i, x2)):
+        (k0, b0), (k1, b1), (k2, b2) = unflatten(th.astype(np.int64))
+        h1 = np.abs(inp) @ np.abs(k0) + np.abs(b0)
+        h2 = h1 @ np.abs(k1) + np.abs(b1)
+        q = h2 @ np.abs(k2) + np.abs(b2)
+        worst = max(worst, int(h1.max()), int(h2.max()), int(q.max()))
+        qmax = q
+    (k0, b0), (k1, b1), (k2, b2) = unflatten(np.abs(theta_i.astype(np.int64)))
+    h1, h2, q = forward(np.abs(theta_i.astype(np.int64)), np.abs(x))
+    delta = q.max(axis=1) + np.abs(r) + qmax.max(axis=1)                 # |Q(s)[a]| + |r| + |f|, each bounded by its sum of |terms|
+    dq = np.repeat(delta[:, None], 3, axis=1)
+    dh2 = dq @ k2.T
+    dh1 = dh2 @ k1.T
+    sums = flatten([(np.abs(x).T @ dh1, dh1.sum(axis=0)), (h1.T @ dh2, dh2.sum(axis=0)), (h2.T @ dq, dq.sum(axis=0))])
+    worst = max(worst, int(delta.max()), int(dh2.max()), int(dh1.max()), int(sums.max()))
+    S = np.rint(out["S"]).astype(np.int64)
+    assert np.array_equal(S.astype(np.float64), out["S"])
+    return worst, S, out
+
+
+def adam64(theta, theta_t, m, v, t, g, lr, tau, beta1=BETA1, beta2=BETA2, eps=EPS):
+    """float64 formulas on the float32 state: -> (theta', theta_t', m', v', t + 1), all float64"""
+    theta, theta_t, m, v, g = (np.asarray(z, dtype=np.float32).astype(np.float64) for z in (theta, theta_t, m, v, g))
+    t = int(t) + 1
+    lr_t = lr * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    m2 = beta1 * m + (1.0 - beta1) * g
+    v2 = beta2 * v + (1.0 - beta2) * g * g
+    th = theta - lr_t * m2 / (np.sqrt(v2) + eps)
+    return th, m2, v2, t
+
+
+def soft64(theta_new32, theta_t32, tau):
+    return tau * theta_new32.astype(np.float64) + (1.0 - tau) * theta_t32.astype(np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+def int_layers(variant="plain", salt=0):
+    """banded integer networks: entries in {-1, 0, 1}, at most 8 non-zeros per row and column"""
+    def band(rows, cols, width, step, mul):
+        i, j = np.arange(rows)[:, None], np.arange(cols)[None, :]
+        inside = ((j - step * i) % cols) < width
+        return (inside * (((mul[0] * i + mul[1] * j + (i * j) // 5 + salt) % 3 != 0) * 2 - 1)).astype(np.float32)
+    k0 = band(5, 64, 8, 13, (2, 1))
+    k1 = band(64, 64, 8, 1, (1, 2))
+    i, c = np.arange(64)[:, None], np.arange(3)[None, :]
+    k2 = ((((3 * i + c) % 8) == 0) * ((i // 8 + c + salt) % 2 * 2 - 1)).astype(np.float32)
+    b0 = np.array([1, 0, 1, -1], dtype=np.float32)[(np.arange(64) + salt) % 4]
+    b1 = np.array([1, 1, -1, 0, 1], dtype=np.float32)[(np.arange(64) + 2 * salt) % 5]
+    b2 = np.array([1, -1, 0], dtype=np.float32)
+    if variant == "tie01":
+        k2[:, 1], b2[1] = k2[:, 0], b2[0]
+    elif variant == "tie012":
+        k2[:, 1], k2[:, 2], b2[1], b2[2] = k2[:, 0], k2[:, 0], b2[0], b2[0]
+    layers = [(k0, b0), (k1, b1), (k2, b2)]
+    for k, _ in layers:
+        assert (np.count_nonzero(k, axis=0) <= 8).all() and (np.count_nonzero(k, axis=1) <= 8).all()
+    return layers
+
+
+def int_ring(cap, size, seed, bad_ok=0.0):
+    """observations in {0, 1}, integer rewards, every termination code; slots behind `size` hold values that would
+    break any sum they entered"""
+    rng = np.random.RandomState(seed)
+    ring = dict(s=rng.randint(0, 2, (5, cap)).astype(np.float32), s2=rng.randint(0, 2, (5, cap)).astype(np.float32),
+                a=rng.randint(0, 3, cap).astype(np.uint8), r=rng.randint(-3, 4, cap).astype(np.float32),
+                d=(rng.randint(0, 4, cap) * (rng.rand(cap) < 0.4)).astype(np.uint8),
+                ok=(rng.rand(cap) >= bad_ok).astype(np.uint8), size=size)
+    for key in ("s", "s2"):
+        ring[key][:, size:] = 3.0e30
+    ring["r"][size:] = 3.0e30
+    ring["ok"][size:] = 1
+    return ring
+
+
+def float_ring(cap, size, seed, bad_ok=0.02):
+    rng = np.random.RandomState(seed)
+    ring = dict(s=rng.rand(5, cap).astype(np.float32), s2=rng.rand(5, cap).astype(np.float32),
+                a=rng.randint(0, 3, cap).astype(np.uint8), r=rng.uniform(-1, 1, cap).astype(np.float32),
+                d=(rng.randint(1, 4, cap) * (rng.rand(cap) < 0.1)).astype(np.uint8),
+                ok=(rng.rand(cap) >= bad_ok).astype(np.uint8), size=size)
+    return ring
+
+
+def random_layers(seed, x32):
+    """N(0, 1) weights, biases of both signs; the last bias is minus each Q column's batch mean (the recipe of
+    tests/test_qpolicy_gpu.py::_random_layers, restated)"""
+    rng = np.random.RandomState(seed)
+    layers = [(rng.randn(a, b).astype(np.float32), rng.randn(b).astype(np.float32)) for a, b in SHAPES]
+    layers[2] = (layers[2][0], np.zeros(3, dtype=np.float32))
+    q = forward(flatten(layers).astype(np.float64), x32.astype(np.float64))[2]
+    layers[2] = (layers[2][0], (-q.mean(axis=0)).astype(np.float32))
+    return layers
+
+
+def glorot_layers(seed):
+    rng = np.random.RandomState(seed)
+    out = []
+    for i, o in SHAPES:
+        lim = np.sqrt(6.0 / (i + o))
+        out.append((rng.uniform(-lim, lim, (i, o)).astype(np.float32), np.zeros(o, dtype=np.float32)))
+    return out
+
+
+class DeviceRing(object):
+    """what DQNLearner.update reads of a ReplayRing, from a numpy ring"""
+
+    def __init__(self, torch, ring, device):
+        for key in ("s", "s2", "r", "a", "d", "ok"):
+            setattr(self, key, torch.as_tensor(np.ascontiguousarray(ring[key])).to(device))
+        self.capacity = int(ring["a"].shape[0])
+        self.size = int(ring["size"])

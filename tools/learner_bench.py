@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""One DQN update on a filled ring, timed on the GPU: libaqua_learner.so (eager, and replayed from a HIP graph) against
+the same update written with torch on the same tensors (three forwards of the 5-64-64-3 MLP, autograd,
+torch.optim.Adam(eps=1e-7), lerp_).  Both draw nothing: the indices are given.  HIP events around REPS updates, after a
+warm-up of every shape, median of ROUNDS regions, the two sides alternating; prints one JSON line per batch size.
+
+    python tools/learner_bench.py [--sizes 64 4096 65536] [--reps 200] [--rounds 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--sizes", type=int, nargs="+", default=[64, 4096, 65536])
+ap.add_argument("--reps", type=int, default=200)
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--capacity", type=int, default=1 << 20)
+args = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("learner_bench needs a GPU: a time taken elsewhere says nothing")
+from aquaticgymenv_amd.learner import DQNLearner
+from aquaticgymenv_amd.qpolicy import QNetwork
+
+DEV = torch.device("cuda:0")
+GAMMA, TAU, LR = 0.98, 0.005, 1e-3
+
+
+class Ring(object):
+    pass
+
+
+g = torch.Generator(device=DEV).manual_seed(1)
+ring = Ring()
+ring.capacity = ring.size = args.capacity
+ring.s = torch.rand((5, ring.capacity), device=DEV, generator=g)
+ring.s2 = torch.rand((5, ring.capacity), device=DEV, generator=g)
+ring.r = torch.rand(ring.capacity, device=DEV, generator=g) - 1.0
+ring.a = torch.randint(0, 3, (ring.capacity,), device=DEV, generator=g, dtype=torch.uint8)
+ring.d = (torch.rand(ring.capacity, device=DEV, generator=g) < 0.05).to(torch.uint8)
+ring.ok = torch.ones(ring.capacity, dtype=torch.uint8, device=DEV)
+
+rng = np.random.RandomState(0)
+layers = []
+for fi, fo in ((5, 64), (64, 64), (64, 3)):
+    lim = np.sqrt(6.0 / (fi + fo))
+    layers.append((rng.uniform(-lim, lim, (fi, fo)).astype(np.float32), np.zeros(fo, dtype=np.float32)))
+
+
+def torch_side():
+    """dqn.py:262-272 + 238-249 + 294-299 with torch: -> update(idx)"""
+    online = [torch.tensor(z, device=DEV, requires_grad=True) for kb in layers for z in kb]
+    target = [p.detach().clone() for p in online]
+    opt = torch.optim.Adam(online, lr=LR, betas=(0.9, 0.999), eps=1e-7)
+
+    def net(p, x):
+        h = torch.relu(x @ p[0] + p[1])
+        h = torch.relu(h @ p[2] + p[3])
+        return h @ p[4] + p[5]
+
+    def update(idx):
+        s, s2 = ring.s[:, idx].t(), ring.s2[:, idx].t()
+        a, r, done = ring.a[idx].long(), ring.r[idx], ring.d[idx] != 0
+        with torch.no_grad():
+            best = net(online, s).argmax(dim=1)                      # dqn.py:267: at b_state
+            future = net(target, s2).gather(1, best[:, None])[:, 0]
+            y = r + torch.where(done, torch.zeros_like(future), GAMMA * future)
+        q = net(online, s).gather(1, a[:, None])[:, 0]
+        loss = ((q - y) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        with torch.no_grad():
+            for t, p in zip(target, online):
+                t.lerp_(p, TAU)
+        return loss
+    return update
+
+
+def region(fn, reps):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    stop.record()
+    stop.synchronize()
+    return 1000.0 * start.elapsed_time(stop) / reps                  # microseconds per update
+
+
+for B in args.sizes:
+    idx = torch.randint(0, ring.size, (B,), device=DEV, generator=g)
+    idx32 = idx.to(torch.int32)
+    learner = DQNLearner(QNetwork(layers, DEV), gamma=GAMMA, tau=TAU, lr=LR)
+    tupdate = torch_side()
+    eager = lambda: learner.update(ring, B, idx=idx32)
+    ref = lambda: tupdate(idx)
+    for _ in range(10):
+        eager()
+        ref()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(10):
+            learner.update(ring, B, idx=idx32)
+    graph.replay()
+    torch.cuda.synchronize()
+    times = {"fused_eager": [], "fused_graph": [], "torch": []}
+    for _ in range(args.rounds):
+        times["fused_eager"].append(region(eager, args.reps))
+        times["torch"].append(region(ref, max(args.reps // 4, 10)))
+        times["fused_graph"].append(region(graph.replay, max(args.reps // 10, 1)) / 10.0)
+    row = {"batch": B, "unit": "us per update", "reps": args.reps, "rounds": args.rounds}
+    for k, v in times.items():
+        row[k] = {"median": round(float(np.median(v)), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+    row["torch_over_fused_eager"] = round(row["torch"]["median"] / row["fused_eager"]["median"], 2)
+    print(json.dumps(row), flush=True)
