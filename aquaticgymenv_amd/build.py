@@ -36,6 +36,13 @@ LEARNER_DEPS = LEARNER_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
 LEARNER_LIB = os.path.join(HERE, "lib", "libaqua_learner.so")
 LEARNER_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_learner"]
 
+# libaqua_episodes.so (include/aqua_episodes.h): episode accounting and the exploration pass, a fourth translation unit and library.
+EPISODES_SRC = [os.path.join(HERE, "csrc", "aqua_episodes.hip")]
+EPISODES_DEPS = EPISODES_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
+                                os.path.join(os.path.dirname(HERE), "include", "aqua_episodes.h")]
+EPISODES_LIB = os.path.join(HERE, "lib", "libaqua_episodes.so")
+EPISODES_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_episodes"]
+
 
 def hipcc_path():
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
@@ -104,6 +111,26 @@ def build_learner(force=False, verbose=False, extra_flags=()):
     return LEARNER_LIB
 
 
+def episodes_needs_build():
+    if not os.path.exists(EPISODES_LIB):
+        return True
+    t = os.path.getmtime(EPISODES_LIB)
+    return any(os.path.getmtime(d) > t for d in EPISODES_DEPS)
+
+
+def build_episodes(force=False, verbose=False, extra_flags=()):
+    """Compile csrc/aqua_episodes.hip -> lib/libaqua_episodes.so for gfx950.  Returns the library path."""
+    if not force and not episodes_needs_build():
+        return EPISODES_LIB
+    os.makedirs(os.path.dirname(EPISODES_LIB), exist_ok=True)
+    cmd = [hipcc_path(), *EPISODES_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", EPISODES_LIB + ".tmp", *EPISODES_SRC]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(EPISODES_LIB + ".tmp", EPISODES_LIB)
+    return EPISODES_LIB
+
+
 def build_variant(name, flags, verbose=False):
     """Tuning builds for A/B timing (tools/ablate.py): lib/variants/libaqua_hip_<name>.so with extra -D flags.
     Select one at run time with AQUA_HIP_LIB=<path>."""
@@ -154,3 +181,4 @@ if __name__ == "__main__":
     print(build_hip(force="--force" in sys.argv, verbose=True))
     print(build_policy(force="--force" in sys.argv, verbose=True))
     print(build_learner(force="--force" in sys.argv, verbose=True))
+    print(build_episodes(force="--force" in sys.argv, verbose=True))

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Replay one of the reference's trained DQN policies (5-64-64-3 MLP, weights committed as a test fixture, read from
 the reference's SavedModel without TensorFlow by aquaticgymenv_amd.tf_import, evaluated by aquaticgymenv_amd.qpolicy.QNetwork
--- tf_import.GreedyQPolicy is the same network as torch GEMMs) on a batch of worlds, recording the
-transitions into the device-side experience ring the way main/impl/dqn.py:174 appends them to its deque.
+-- tf_import.GreedyQPolicy is the same network as torch GEMMs) on a batch of worlds: first one episode per world, the way
+Policy.test / TestPlotter.run_tests of the reference evaluate a policy (aquaticgymenv_amd.episodes.evaluate), then 500 steps
+with restarts, recording the transitions into the device-side experience ring the way main/impl/dqn.py:174 appends them to
+its deque.
 
     python examples/dqn_replay.py [--envs 16384] [--obstacles]
 """
@@ -15,6 +17,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from aquaticgymenv_amd.batched import BatchedAqua
+from aquaticgymenv_amd.episodes import evaluate
 from aquaticgymenv_amd.replay import ReplayRing
 from aquaticgymenv_amd.qpolicy import QNetwork
 
@@ -27,21 +30,23 @@ z = np.load(os.path.join(ROOT, "tests", "golden", "dqn_policies.npz"))
 tag = "with_obs" if args.obstacles else "no_obs"
 qnet = QNetwork([(z["%s_kernel%d" % (tag, i)], z["%s_bias%d" % (tag, i)]) for i in range(3)], "cuda")
 
+# one episode per world, no restarts: the protocol of the published figures
+runs = BatchedAqua(args.envs, obstacles=args.obstacles, seed=2, auto_reset=False)
+runs.reset()
+result = evaluate(runs, qnet)
+print("%d runs, %d finished: %.1f %% reached the goal (published: %.1f %%), mean reward %.2f (published %.2f), mean steps %.1f" %
+      (args.envs, int((result["Code"] != 0).sum()), 100.0 * float(result["Success"].mean()),
+       100.0 * float(z["%s_published_success" % tag].mean()), float(result["Reward"].mean()),
+       float(z["%s_published_reward" % tag].mean()), float(result["Steps"].mean())))
+
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=2, auto_reset="next_step", normalized_obs=True)
 env.reset()
 ring = ReplayRing(env, capacity=64 * args.envs)
-episodes = success = 0
 for step in range(500):
     action = qnet.act(env, out=env.policy_action)          # argmax_a Q(s, a): one launch of our own kernel (epsilon=... explores)
     ring.before_step(env.policy_action)
     obs, reward, term = env.step(action)
     ring.after_step()
-    episodes += int((term != 0).sum())
-    success += int((term == 3).sum())
-# (all episodes that ended within 500 steps: short, i.e. failed, episodes are over-represented against the published
-#  one-episode-per-run figure, which tests/test_hip_parity.py reproduces exactly that way)
-print("%d episodes finished, %.1f %% reached the goal (published, one episode per run: %.1f %%)" %
-      (episodes, 100.0 * success / max(episodes, 1), 100.0 * float(z["%s_published_success" % tag].mean())))
 s, a, r, s2, done = ring.sample(256)
 q_next = qnet.q_values(ring.s2, ring.size)                 # Q(s', .) of the whole ring for TD targets (dqn.py:262-292): [3][size]
 print("ring holds %d transitions; a sampled minibatch: s %s a %s r %s s' %s done %s" %

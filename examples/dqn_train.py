@@ -4,8 +4,11 @@ epsilon-greedy Q-network picks the actions (libaqua_policy.so), one batched step
 the device experience ring, and DQNLearner (libaqua_learner.so) performs the update -- TD target, gradient, Adam, soft
 target update -- and re-packs the acting network's weights in place.
 
-One batched step here is N steps of the reference, and one update of --batch samples follows it; epsilon decays per
-finished episode as dqn.py:184 does.  The success rate of the episodes finished in every 100 steps is printed.
+One batched step here is N steps of the reference, and one update of --batch samples follows it.  The episodes are kept by
+an EpisodeTracker (libaqua_episodes.so) on the device: return and length per world, the log of finished episodes, and
+epsilon, which decays once per finished episode as dqn.py:184 does and is read by the exploration pass where it lives.
+Every 100 steps the line of dqn.py:194-200 is printed from the tracker -- mean return, mean length and success rate of the
+last 100 episodes, epsilon; that print is the only host read of the loop.
 
     python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles]
 """
@@ -18,6 +21,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from aquaticgymenv_amd.batched import BatchedAqua
+from aquaticgymenv_amd.episodes import EpisodeTracker
 from aquaticgymenv_amd.learner import DQNLearner
 from aquaticgymenv_amd.qpolicy import QNetwork
 from aquaticgymenv_amd.replay import ReplayRing
@@ -34,7 +38,6 @@ args = ap.parse_args()
 
 # default_hyperparam of dqn.py
 EPS_INIT, EPS_FINAL, GAMMA, TAU = 1.0, 0.05, 0.98, 0.005
-decay = args.epsilon_decay if args.epsilon_decay < 1 else (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)
 
 rng = np.random.RandomState(args.seed)
 layers = []
@@ -47,23 +50,21 @@ learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref",
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()
 ring = ReplayRing(env, capacity=max(args.buffer, args.envs))
-epsilon = EPS_INIT
-finished = torch.zeros((), dtype=torch.int64, device=env.device)
-succeeded = torch.zeros((), dtype=torch.int64, device=env.device)
+tracker = EpisodeTracker(env, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))     # decay >= 1: episodes to reach EPS_FINAL
 for step in range(1, args.steps + 1):
-    # env.step(policy=qnet, epsilon=...) in two calls, so that the ring sees the action before the step
-    action = qnet.act(env, epsilon=epsilon, out=env.policy_action)
+    # env.step(policy=qnet, epsilon=...) in three calls: greedy actions, the exploring draws under the device epsilon, and
+    # the step, so that the ring sees the action before the step
+    action = qnet.act(env, epsilon=0.0, out=env.policy_action)
+    tracker.explore(env.policy_action)
     ring.before_step(env.policy_action)
     obs, reward, term = env.step(action)
     ring.after_step()
+    tracker.after_step()                                       # returns, lengths, the log, epsilon: all on the device
     learner.update(ring, args.batch)                           # minibatch drawn on the device; qnet acts with the new weights
-    finished += (term != 0).sum()
-    succeeded += (term == 3).sum()
     if step % 100 == 0:                                        # the only host reads of the loop
-        n, ok = int(finished), int(succeeded)
-        epsilon = max(epsilon * decay ** n, EPS_FINAL)         # dqn.py:184, once per finished episode
-        print("step %6d  episodes %6d  success %5.1f %%  loss %10.4f  epsilon %.3f  ring %d" %
-              (step, n, 100.0 * ok / max(n, 1), float(learner.loss), epsilon, ring.size))
-        finished.zero_()
-        succeeded.zero_()
+        c, last = tracker.counts(), tracker.last(100)
+        k = max(len(last["ret"]), 1)
+        print("step %6d  episodes %7d  mean_last_100: reward %8.2f  steps %6.1f  success %3.0f %%  loss %10.4f  epsilon %.3f  ring %d" %
+              (step, c["episodes"], float(last["ret"].sum()) / k, float(last["len"].sum()) / k,
+               100.0 * float((last["code"] == 3).sum()) / k, float(learner.loss), float(tracker.epsilon), ring.size))
 learner.weights()                                              # qnet.layers now holds the trained network
