@@ -1,10 +1,10 @@
 """ctypes binding of libaqua_episodes.so (include/aqua_episodes.h).  No fallback: if the HIP library is missing or does
 not load, importing this module raises -- episode accounting has no CPU path."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AQUA_EPISODES_LIB") or os.path.join(_HERE, "lib", "libaqua_episodes.so")
+from . import _loader
+
+LIB_PATH = _loader.lib_path("AQUA_EPISODES_LIB", "libaqua_episodes.so")
 
 ABI_VERSION = 1
 E_INVALID, E_ALIGN, E_NODEVICE = -1, -2, -3
@@ -21,38 +21,17 @@ class AquaEpisodesError(RuntimeError):
     pass
 
 
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "libaqua_episodes.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
-            "`python -m aquaticgymenv_amd.build` (needs hipcc); there is no CPU fallback")
-    # torch's libamdhip64 first, so that this library's NEEDED entry resolves to the same runtime (see _capi.py)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, i64, u64, ci, cd = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double
-    lib.aquaep_version.restype = ci
-    lib.aquaep_last_error.restype = ctypes.c_char_p
-    lib.aquaep_workspace_bytes.argtypes = [i64]
-    lib.aquaep_workspace_bytes.restype = ctypes.c_size_t
-    lib.aquaep_after_step_f32.argtypes = [vp, vp, vp, i64, i64,               # reward, term, time, env_offset, N
-                                          vp, vp, vp,                         # ret, len, finished
-                                          vp, vp, vp, vp, i64,                # log_ret, log_len, log_code, log_world, C
-                                          vp, vp, vp, cd, cd,                 # counts, eps_state, eps_out, decay, eps_final
-                                          vp, ctypes.c_size_t, vp]            # workspace, workspace_bytes, stream
-    lib.aquaep_after_step_f32.restype = ci
-    lib.aquaep_explore_u8.argtypes = [vp, i64, i64, vp, u64, u64, vp, vp]     # action, N, env_offset, eps, seed, tick, tick_base, stream
-    lib.aquaep_explore_u8.restype = ci
-    if lib.aquaep_version() != ABI_VERSION:
-        raise ImportError("libaqua_episodes.so ABI %d != binding %d: rebuild" % (lib.aquaep_version(), ABI_VERSION))
-    return lib
+_vp, _i64, _u64, _cd, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double, ctypes.c_size_t
+_SIGNATURES = {
+    "aquaep_workspace_bytes": ([_i64], _sz),
+    "aquaep_after_step_f32": ([_vp, _vp, _vp, _i64, _i64,                   # reward, term, time, env_offset, N
+                               _vp, _vp, _vp,                               # ret, len, finished
+                               _vp, _vp, _vp, _vp, _i64,                    # log_ret, log_len, log_code, log_world, C
+                               _vp, _vp, _vp, _cd, _cd,                     # counts, eps_state, eps_out, decay, eps_final
+                               _vp, _sz, _vp], ctypes.c_int),               # workspace, workspace_bytes, stream
+    "aquaep_explore_u8": ([_vp, _i64, _i64, _vp, _u64, _u64, _vp, _vp],     # action, N, env_offset, eps, seed, tick, tick_base, stream
+                          ctypes.c_int),
+}
 
-
-lib = _load()
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = lib.aquaep_last_error().decode("utf-8", "replace")
-        if rc == E_INVALID:
-            raise ValueError("%s: %s" % (what, msg))
-        raise AquaEpisodesError("%s failed (code %d): %s" % (what, rc, msg))
+lib = _loader.load("libaqua_episodes.so", LIB_PATH, "aquaep", ABI_VERSION, _SIGNATURES)
+check = _loader.checker(lib, "aquaep", AquaEpisodesError)

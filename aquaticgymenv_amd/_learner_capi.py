@@ -1,10 +1,10 @@
 """ctypes binding of libaqua_learner.so (include/aqua_learner.h).  No fallback: if the HIP library is missing or does
 not load, importing this module raises -- the DQN update has no CPU path."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AQUA_LEARNER_LIB") or os.path.join(_HERE, "lib", "libaqua_learner.so")
+from . import _loader
+
+LIB_PATH = _loader.lib_path("AQUA_LEARNER_LIB", "libaqua_learner.so")
 
 ABI_VERSION = 1
 E_INVALID, E_ALIGN, E_NODEVICE = -1, -2, -3
@@ -21,41 +21,20 @@ class AquaLearnerError(RuntimeError):
     pass
 
 
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "libaqua_learner.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
-            "`python -m aquaticgymenv_amd.build` (needs hipcc); there is no CPU fallback")
-    # torch's libamdhip64 first, so that this library's NEEDED entry resolves to the same runtime (see _capi.py)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, i64, u64, ci, cd = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double
-    lib.aqualrn_version.restype = ci
-    lib.aqualrn_last_error.restype = ctypes.c_char_p
-    lib.aqualrn_workspace_bytes.argtypes = [i64]
-    lib.aqualrn_workspace_bytes.restype = ctypes.c_size_t
-    lib.aqualrn_update_f32.argtypes = [vp, vp, vp, vp, vp,                 # theta, theta_target, m, v, t
-                                       vp, vp, vp, vp, vp, vp, i64, i64,    # s, a, r, s2, d, ok, ld, size
-                                       vp, i64, u64,                        # idx, B, seed
-                                       ci, cd, cd, cd, cd, cd, cd,          # strategy, gamma, tau, lr, beta1, beta2, eps
-                                       vp, vp, vp, i64,                     # blob_online, blob_target, perm, blob_floats
-                                       vp, ctypes.c_size_t,                 # workspace, workspace_bytes
-                                       vp, vp, vp, vp]                      # idx_out, grad_out, loss, stream
-    lib.aqualrn_update_f32.restype = ci
-    if lib.aqualrn_version() != ABI_VERSION:
-        raise ImportError("libaqua_learner.so ABI %d != binding %d: rebuild" % (lib.aqualrn_version(), ABI_VERSION))
-    return lib
+_vp, _i64, _u64, _ci, _cd, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
+_SIGNATURES = {
+    "aqualrn_workspace_bytes": ([_i64], _sz),
+    "aqualrn_update_f32": ([_vp, _vp, _vp, _vp, _vp,                        # theta, theta_target, m, v, t
+                            _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,       # s, a, r, s2, d, ok, ld, size
+                            _vp, _i64, _u64,                                # idx, B, seed
+                            _ci, _cd, _cd, _cd, _cd, _cd, _cd,              # strategy, gamma, tau, lr, beta1, beta2, eps
+                            _vp, _vp, _vp, _i64,                            # blob_online, blob_target, perm, blob_floats
+                            _vp, _sz,                                       # workspace, workspace_bytes
+                            _vp, _vp, _vp, _vp], _ci),                      # idx_out, grad_out, loss, stream
+}
 
-
-lib = _load()
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = lib.aqualrn_last_error().decode("utf-8", "replace")
-        if rc == E_INVALID:
-            raise ValueError("%s: %s" % (what, msg))
-        raise AquaLearnerError("%s failed (code %d): %s" % (what, rc, msg))
+lib = _loader.load("libaqua_learner.so", LIB_PATH, "aqualrn", ABI_VERSION, _SIGNATURES)
+check = _loader.checker(lib, "aqualrn", AquaLearnerError)
 
 
 def flatten(layers):

@@ -1,10 +1,10 @@
 """ctypes binding of libaqua_policy.so (include/aqua_policy.h).  No fallback: if the HIP library is missing or does
 not load, importing this module raises -- the Q-network has no CPU path."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AQUA_POLICY_LIB") or os.path.join(_HERE, "lib", "libaqua_policy.so")
+from . import _loader
+
+LIB_PATH = _loader.lib_path("AQUA_POLICY_LIB", "libaqua_policy.so")
 
 ABI_VERSION = 1
 E_INVALID, E_ALIGN, E_NODEVICE = -1, -2, -3
@@ -19,36 +19,15 @@ class AquaPolicyError(RuntimeError):
     pass
 
 
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "libaqua_policy.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
-            "`python -m aquaticgymenv_amd.build` (needs hipcc); there is no CPU fallback")
-    # torch's libamdhip64 first, so that this library's NEEDED entry resolves to the same runtime (see _capi.py)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, i64, u64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_float
-    lib.aquapol_version.restype = ci
-    lib.aquapol_last_error.restype = ctypes.c_char_p
-    lib.aquapol_weights_bytes.restype = ctypes.c_size_t
-    lib.aquapol_pack_weights.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci), vp, ctypes.c_size_t]
-    lib.aquapol_pack_weights.restype = ci
-    lib.aquapol_act_f32.argtypes = [vp, vp, i64, ci, i64, i64, cf, u64, u64, vp, vp, vp, i64, vp, vp]
-    lib.aquapol_act_f32.restype = ci
-    if lib.aquapol_version() != ABI_VERSION:
-        raise ImportError("libaqua_policy.so ABI %d != binding %d: rebuild" % (lib.aquapol_version(), ABI_VERSION))
-    return lib
+_vp, _i64, _u64, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_SIGNATURES = {
+    "aquapol_weights_bytes": (None, _sz),
+    "aquapol_pack_weights": ([_vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_ci), _vp, _sz], _ci),
+    "aquapol_act_f32": ([_vp, _vp, _i64, _ci, _i64, _i64, _cf, _u64, _u64, _vp, _vp, _vp, _i64, _vp, _vp], _ci),
+}
 
-
-lib = _load()
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = lib.aquapol_last_error().decode("utf-8", "replace")
-        if rc == E_INVALID:
-            raise ValueError("%s: %s" % (what, msg))
-        raise AquaPolicyError("%s failed (code %d): %s" % (what, rc, msg))
+lib = _loader.load("libaqua_policy.so", LIB_PATH, "aquapol", ABI_VERSION, _SIGNATURES)
+check = _loader.checker(lib, "aquapol", AquaPolicyError)
 
 
 def pack_weights(layers):

@@ -3,16 +3,13 @@
 The shared object lands in aquaticgymenv_amd/lib/ so that it travels with the source tree to the
 GPU box (a JIT cache under $HOME would not).  hipcc cross-compiles for gfx950 without a GPU.
 """
+import functools
 import os
 import shutil
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", "aqua_hip.hip")]
-DEPS = SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"), os.path.join(HERE, "csrc", "aqua_tuning.inc"),
-              os.path.join(os.path.dirname(HERE), "include", "aqua_hip.h")]
-LIB = os.path.join(HERE, "lib", "libaqua_hip.so")
 ARCH = "gfx950"
 # -fno-honor-nans: no state ever holds a NaN; it drops the v_max(x, x) canonicalisation in front of every
 # fmin/fmax (results for non-NaN inputs are unchanged; contraction is controlled per function by pragmas)
@@ -21,27 +18,26 @@ ARCH = "gfx950"
 # tag of bench.py and profiles/traffic.json) depends on the sources and this command line only.
 COMMON_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-std=c++17", "-shared", "-fPIC", "-fno-honor-nans", "-cuid=aqua_hip"]
 
-# libaqua_policy.so (include/aqua_policy.h): the Q-network kernel, a translation unit and a library of its own -- the
-# command line and the hash of libaqua_hip.so do not depend on it.  Same flags, its own compilation-unit id.
-POLICY_SRC = [os.path.join(HERE, "csrc", "aqua_policy.hip")]
-POLICY_DEPS = POLICY_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
-                            os.path.join(os.path.dirname(HERE), "include", "aqua_policy.h")]
-POLICY_LIB = os.path.join(HERE, "lib", "libaqua_policy.so")
-POLICY_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_policy"]
 
-# libaqua_learner.so (include/aqua_learner.h): the DQN update, again a translation unit and a library of its own.
-LEARNER_SRC = [os.path.join(HERE, "csrc", "aqua_learner.hip")]
-LEARNER_DEPS = LEARNER_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
-                              os.path.join(os.path.dirname(HERE), "include", "aqua_learner.h")]
-LEARNER_LIB = os.path.join(HERE, "lib", "libaqua_learner.so")
-LEARNER_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_learner"]
+def _library(name, headers):
+    """csrc/aqua_<name>.hip + include/aqua_<name>.h -> lib/libaqua_<name>.so, a translation unit and a library of its own:
+    the common flags with its own compilation-unit id.  headers: what the source includes from csrc/."""
+    src, cuid = [os.path.join(HERE, "csrc", "aqua_%s.hip" % name)], "aqua_" + name
+    return {"src": src,
+            "deps": src + [os.path.join(HERE, "csrc", h) for h in headers] + [os.path.join(os.path.dirname(HERE), "include", "aqua_%s.h" % name)],
+            "lib": os.path.join(HERE, "lib", "libaqua_%s.so" % name),
+            "cuid": cuid,
+            "flags": [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=" + cuid]}
 
-# libaqua_episodes.so (include/aqua_episodes.h): episode accounting and the exploration pass, a fourth translation unit and library.
-EPISODES_SRC = [os.path.join(HERE, "csrc", "aqua_episodes.hip")]
-EPISODES_DEPS = EPISODES_SRC + [os.path.join(HERE, "csrc", "aqua_device.hpp"),
-                                os.path.join(os.path.dirname(HERE), "include", "aqua_episodes.h")]
-EPISODES_LIB = os.path.join(HERE, "lib", "libaqua_episodes.so")
-EPISODES_FLAGS = [f for f in COMMON_FLAGS if not f.startswith("-cuid=")] + ["-cuid=aqua_episodes"]
+
+# In build order.  hip: the environment (include/aqua_hip.h); its command line and hash depend on none of the others.
+# policy: the Q-network kernel; learner: the DQN update; episodes: episode accounting and the exploration pass.
+LIBRARIES = {
+    "hip": _library("hip", ["aqua_device.hpp", "aqua_tuning.inc"]),
+    "policy": _library("policy", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+    "learner": _library("learner", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+    "episodes": _library("episodes", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
 
 
 def hipcc_path():
@@ -51,84 +47,41 @@ def hipcc_path():
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm)")
 
 
-def needs_build():
-    if not os.path.exists(LIB):
+def needs_build(name="hip"):
+    entry = LIBRARIES[name]
+    if not os.path.exists(entry["lib"]):
         return True
-    t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(d) > t for d in DEPS)
+    t = os.path.getmtime(entry["lib"])
+    return any(os.path.getmtime(d) > t for d in entry["deps"])
 
 
-def build_hip(force=False, verbose=False, extra_flags=()):
-    """Compile csrc/aqua_hip.hip -> lib/libaqua_hip.so for gfx950.  Returns the library path."""
-    if not force and not needs_build():
-        return LIB
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    cmd = [hipcc_path(), *COMMON_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", LIB + ".tmp", *SRC]
+def build_command(name, extra_flags=()):
+    """the hipcc command line of build_library(name), without running it"""
+    entry = LIBRARIES[name]
+    return [hipcc_path(), *entry["flags"], "-Wall", "-Wno-unused-function", *extra_flags, "-o", entry["lib"] + ".tmp", *entry["src"]]
+
+
+def build_library(name, force=False, verbose=False, extra_flags=()):
+    """Compile the library's source -> lib/libaqua_<name>.so for gfx950.  Returns the library path."""
+    lib = LIBRARIES[name]["lib"]
+    if not force and not needs_build(name):
+        return lib
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
+    cmd = build_command(name, extra_flags)
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
-    os.replace(LIB + ".tmp", LIB)
-    return LIB
+    os.replace(lib + ".tmp", lib)
+    return lib
 
 
-def policy_needs_build():
-    if not os.path.exists(POLICY_LIB):
-        return True
-    t = os.path.getmtime(POLICY_LIB)
-    return any(os.path.getmtime(d) > t for d in POLICY_DEPS)
-
-
-def build_policy(force=False, verbose=False, extra_flags=()):
-    """Compile csrc/aqua_policy.hip -> lib/libaqua_policy.so for gfx950 (a few seconds).  Returns the library path."""
-    if not force and not policy_needs_build():
-        return POLICY_LIB
-    os.makedirs(os.path.dirname(POLICY_LIB), exist_ok=True)
-    cmd = [hipcc_path(), *POLICY_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", POLICY_LIB + ".tmp", *POLICY_SRC]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(POLICY_LIB + ".tmp", POLICY_LIB)
-    return POLICY_LIB
-
-
-def learner_needs_build():
-    if not os.path.exists(LEARNER_LIB):
-        return True
-    t = os.path.getmtime(LEARNER_LIB)
-    return any(os.path.getmtime(d) > t for d in LEARNER_DEPS)
-
-
-def build_learner(force=False, verbose=False, extra_flags=()):
-    """Compile csrc/aqua_learner.hip -> lib/libaqua_learner.so for gfx950.  Returns the library path."""
-    if not force and not learner_needs_build():
-        return LEARNER_LIB
-    os.makedirs(os.path.dirname(LEARNER_LIB), exist_ok=True)
-    cmd = [hipcc_path(), *LEARNER_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", LEARNER_LIB + ".tmp", *LEARNER_SRC]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(LEARNER_LIB + ".tmp", LEARNER_LIB)
-    return LEARNER_LIB
-
-
-def episodes_needs_build():
-    if not os.path.exists(EPISODES_LIB):
-        return True
-    t = os.path.getmtime(EPISODES_LIB)
-    return any(os.path.getmtime(d) > t for d in EPISODES_DEPS)
-
-
-def build_episodes(force=False, verbose=False, extra_flags=()):
-    """Compile csrc/aqua_episodes.hip -> lib/libaqua_episodes.so for gfx950.  Returns the library path."""
-    if not force and not episodes_needs_build():
-        return EPISODES_LIB
-    os.makedirs(os.path.dirname(EPISODES_LIB), exist_ok=True)
-    cmd = [hipcc_path(), *EPISODES_FLAGS, "-Wall", "-Wno-unused-function", *extra_flags, "-o", EPISODES_LIB + ".tmp", *EPISODES_SRC]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(EPISODES_LIB + ".tmp", EPISODES_LIB)
-    return EPISODES_LIB
+# the names that tests, tools and __graft_entry__ use, bound from the table
+SRC, DEPS, LIB = (LIBRARIES["hip"][k] for k in ("src", "deps", "lib"))
+POLICY_SRC, POLICY_DEPS, POLICY_LIB, POLICY_FLAGS = (LIBRARIES["policy"][k] for k in ("src", "deps", "lib", "flags"))
+LEARNER_SRC, LEARNER_DEPS, LEARNER_LIB, LEARNER_FLAGS = (LIBRARIES["learner"][k] for k in ("src", "deps", "lib", "flags"))
+EPISODES_SRC, EPISODES_DEPS, EPISODES_LIB, EPISODES_FLAGS = (LIBRARIES["episodes"][k] for k in ("src", "deps", "lib", "flags"))
+build_hip, build_policy, build_learner, build_episodes = (functools.partial(build_library, n) for n in LIBRARIES)
+policy_needs_build, learner_needs_build, episodes_needs_build = (functools.partial(needs_build, n) for n in ("policy", "learner", "episodes"))
 
 
 def build_variant(name, flags, verbose=False):
@@ -178,7 +131,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    print(build_hip(force="--force" in sys.argv, verbose=True))
-    print(build_policy(force="--force" in sys.argv, verbose=True))
-    print(build_learner(force="--force" in sys.argv, verbose=True))
-    print(build_episodes(force="--force" in sys.argv, verbose=True))
+    for name in LIBRARIES:
+        print(build_library(name, force="--force" in sys.argv, verbose=True))

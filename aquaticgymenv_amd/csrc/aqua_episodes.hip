@@ -12,21 +12,19 @@
 // No block waits on another block; no fence, flag or ticket; no floating-point atomics.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "../../include/aqua_episodes.h"
 #include "aqua_device.hpp"
+#include "aqua_host.hpp"
+#include "aqua_qnet.hpp"
 
 namespace {
 
 using aqua::draw;
 using aqua::u_01;
+using aqua::qnet::random_action;
+using aqua::qnet::STREAM_POLICY;
 
-constexpr uint32_t STREAM_EXPLORE = AQUAEP_STREAM;      // the policy's stream: the pass reproduces the policy kernel's draw
-static_assert(STREAM_EXPLORE != aqua::STREAM_STEP && STREAM_EXPLORE != aqua::STREAM_PLACE && STREAM_EXPLORE != aqua::STREAM_POSE &&
-              STREAM_EXPLORE != aqua::STREAM_ACT, "the exploration draws are not the environment's");
+static_assert(STREAM_POLICY == AQUAEP_STREAM, "the exploration pass reproduces the policy kernel's draw: the policy's stream");
 
 constexpr int BLOCK = 256, WAVES = BLOCK / 64;
 constexpr int MAX_BLOCKS = AQUAEP_MAX_BLOCKS;
@@ -224,39 +222,12 @@ __global__ __launch_bounds__(BLOCK) void ep_explore_kernel(const ExploreArgs a)
         uint32_t r[4];
         // (the scalar-key form: the seed is a kernel argument; as plain draw() the ten round keys are hoisted out of the loop
         // into SGPRs that spill.  The same ten rounds, the same bits as the policy kernel's draw)
-        draw<true>(a.seed, static_cast<uint64_t>(a.env_offset + i), tick, STREAM_EXPLORE, 0, r);
-        if (u_01(r[0]) < eps) a.action[i] = static_cast<uint8_t>(((r[1] >> 8) * 3u) >> 24);
+        draw<true>(a.seed, static_cast<uint64_t>(a.env_offset + i), tick, STREAM_POLICY, 0, r);
+        if (u_01(r[0]) < eps) a.action[i] = static_cast<uint8_t>(random_action(r));
     }
 }
 
 // ------------------------------------------------------------------ host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* what)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return static_cast<int>(e);
-}
-
-// NaN and infinity by their bits: the library is built with -fno-honor-nans, which lets the compiler drop x != x
-bool is_number(double x)
-{
-    uint64_t bits;
-    std::memcpy(&bits, &x, sizeof(bits));
-    return ((bits >> 52) & 0x7FFu) != 0x7FFu;
-}
-
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // the launch shape: a function of N alone
 struct Shape {
     int64_t chunk;

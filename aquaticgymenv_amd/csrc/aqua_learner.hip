@@ -28,27 +28,23 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 
 #include "../../include/aqua_learner.h"
 #include "aqua_device.hpp"
+#include "aqua_host.hpp"
+#include "aqua_qnet.hpp"
 
 namespace {
 
 using aqua::draw;
+using namespace aqua::qnet;
 
-constexpr uint32_t STREAM_LEARNER = AQUALRN_STREAM;     // aqua_device.hpp: 0, 1, 3, 4 are the environment's; 5 the policy's
-static_assert(STREAM_LEARNER != aqua::STREAM_STEP && STREAM_LEARNER != aqua::STREAM_PLACE && STREAM_LEARNER != aqua::STREAM_POSE &&
-              STREAM_LEARNER != aqua::STREAM_ACT && STREAM_LEARNER != 5, "the minibatch draws need a stream of their own");
+static_assert(STREAM_LEARNER == AQUALRN_STREAM, "aqua_learner.h names the stream of the minibatch draws");
 
-constexpr int IN = 5, HID = 64, ACT = 3;
 constexpr int OFF_K0 = 0, OFF_B0 = OFF_K0 + IN * HID, OFF_K1 = OFF_B0 + HID, OFF_B1 = OFF_K1 + HID * HID;
 constexpr int OFF_K2 = OFF_B1 + HID, OFF_B2 = OFF_K2 + HID * ACT, PARAMS = OFF_B2 + ACT;
 static_assert(PARAMS == AQUALRN_PARAMS, "canonical Keras order: k0, b0, k1, b1, k2, b2");
 
-constexpr int TILE = 32;                 // samples per wavefront and pass: the MFMA's column count
 constexpr int WAVES = 2, BLOCK = 64 * WAVES;
 constexpr int GMAX = 512;                // workgroups (= partial gradients) at most
 constexpr int STR = TILE + 1;            // [unit][sample] staging rows, padded: conflict-free writes and reads
@@ -67,11 +63,6 @@ static_assert(WS_USED <= WS_STRIDE && WS_STRIDE % 4 == 0 && WS_LOSS % 2 == 0, "a
 static_assert(WS_STRIDE <= WAVES * 2 * HID * STR, "the workgroup's sum lives in the staging area");
 
 constexpr int APPLY_BLOCK = 64;
-
-// the unit (row of the accumulator tile) that register r of row block M holds on lane half h: unit_of(M, r, h) = UNIT(M, r) + 4 h
-#define UNIT(M, r) static_cast<unsigned>(32 * (M) + ((r) & 3) + 8 * ((r) >> 2))
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
@@ -109,13 +100,13 @@ __device__ __forceinline__ void forward(const float* P, const double* k2d, const
     // h and col are made opaque here: every address below is then one 32-bit add on a lane offset computed in this pass
     // (otherwise the ~250 64-bit addresses of a pass are computed once in front of the tile loop and spilled)
     asm volatile("" : "+v"(h), "+v"(col), "+s"(P));
-    const unsigned ub = 4u * h;                    // unit_of(M, r, h) = UNIT(M, r) + ub
+    const unsigned ub = 4u * h;                    // unit_of(M, r, h) = unit_of(M, r, 0) + ub
 #pragma unroll
     for (int M = 0; M < 2; ++M)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            h1[M][r] = P[OFF_B0 + UNIT(M, r) + ub];
-            h2[M][r] = P[OFF_B1 + UNIT(M, r) + ub];
+            h1[M][r] = P[OFF_B0 + unit_of(M, r, 0) + ub];
+            h2[M][r] = P[OFF_B1 + unit_of(M, r, 0) + ub];
         }
     // (scheduling fences: without them every weight load of a pass is hoisted to its top)
     __builtin_amdgcn_sched_barrier(0);
@@ -137,8 +128,8 @@ __device__ __forceinline__ void forward(const float* P, const double* k2d, const
         for (int r = 0; r < 16; ++r) {
             if ((r & 7) == 0) __builtin_amdgcn_sched_barrier(0);
             const float b = fmaxf(h1[M][r], 0.0f);
-            h2[0] = mfma(P[OFF_K1 + UNIT(M, r) * HID + k1b], b, h2[0]);
-            h2[1] = mfma(P[OFF_K1 + UNIT(M, r) * HID + 32 + k1b], b, h2[1]);
+            h2[0] = mfma(P[OFF_K1 + unit_of(M, r, 0) * HID + k1b], b, h2[0]);
+            h2[1] = mfma(P[OFF_K1 + unit_of(M, r, 0) * HID + 32 + k1b], b, h2[1]);
         }
     __builtin_amdgcn_sched_barrier(0);
     // layer 3: 3 x 64 on the VALU in double from the 32 units this lane holds, then one add across the lane halves
@@ -154,7 +145,7 @@ __device__ __forceinline__ void forward(const float* P, const double* k2d, const
             if ((r & 3) == 0) __builtin_amdgcn_sched_barrier(0);
             const double v = static_cast<double>(fmaxf(h2[M][r], 0.0f));
 #pragma unroll
-            for (int c = 0; c < ACT; ++c) p[c] = fma(k2h[UNIT(M, r) * ACT + c], v, p[c]);
+            for (int c = 0; c < ACT; ++c) p[c] = fma(k2h[unit_of(M, r, 0) * ACT + c], v, p[c]);
         }
 #pragma unroll
     for (int c = 0; c < ACT; ++c) q[c] = p[c] + __shfl_xor(p[c], 32);
@@ -220,9 +211,9 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
         const int wave = tl >> 6, h = (tl >> 5) & 1, col = tl & 31;
         // LDS offsets of this lane, opaque to the compiler so that every access below is base + immediate (otherwise each of
         // the few hundred addresses is computed in front of the loop and kept in a register of its own)
-        unsigned wr = wave * 2 * HID * STR + 4 * h * STR + col;     // [unit_of(M, r, h)][col] of buf0: + UNIT(M, r) * STR
+        unsigned wr = wave * 2 * HID * STR + 4 * h * STR + col;     // [unit_of(M, r, h)][col] of buf0: + unit_of(M, r, 0) * STR
         unsigned rd = wave * 2 * HID * STR + col * STR + h;         // [col][2 st + h] of buf0: + 2 st; second row block: + 32 STR
-        unsigned kt = col * K1T_STR + 4 * h;                        // k1t[col][unit_of(M, r, h)]: + UNIT(M, r)
+        unsigned kt = col * K1T_STR + 4 * h;                        // k1t[col][unit_of(M, r, h)]: + unit_of(M, r, 0)
         asm volatile("" : "+v"(wr), "+v"(rd), "+v"(kt));
         unsigned o2 = SLOT_K0 + (IN + 1) * h + (col <= IN ? col : 0), o3 = SLOT_K2 + ACT * h + (col < ACT ? col : 0), o4 = SLOT_B1 + h;
         asm volatile("" : "+v"(o2), "+v"(o3), "+v"(o4));
@@ -299,7 +290,7 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
 #pragma unroll
         for (int M = 0; M < 2; ++M)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) stage[wr + UNIT(M, r) * STR] = fmaxf(h2[M][r], 0.0f);
+            for (int r = 0; r < 16; ++r) stage[wr + unit_of(M, r, 0) * STR] = fmaxf(h2[M][r], 0.0f);
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
         {
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
         for (int M = 0; M < 2; ++M)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                h2[M][r] = h2[M][r] > 0.0f ? P[OFF_K2 + UNIT(M, r) * ACT + k2a] * delta : 0.0f;
+                h2[M][r] = h2[M][r] > 0.0f ? P[OFF_K2 + unit_of(M, r, 0) * ACT + k2a] * delta : 0.0f;
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
 
@@ -338,8 +329,8 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
         for (int M = 0; M < 2; ++M)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                stage[wr + UNIT(M, r) * STR] = fmaxf(h1[M][r], 0.0f);
-                stage[wr + UNIT(M, r) * STR + HID * STR] = h2[M][r];
+                stage[wr + unit_of(M, r, 0) * STR] = fmaxf(h1[M][r], 0.0f);
+                stage[wr + unit_of(M, r, 0) * STR + HID * STR] = h2[M][r];
             }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
@@ -375,8 +366,8 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if ((r & 7) == 0) __builtin_amdgcn_sched_barrier(0);
-                d1[0] = mfma(k1t[kt + UNIT(M, r)], h2[M][r], d1[0]);
-                d1[1] = mfma(k1t[kt + UNIT(M, r) + 32 * K1T_STR], h2[M][r], d1[1]);
+                d1[0] = mfma(k1t[kt + unit_of(M, r, 0)], h2[M][r], d1[0]);
+                d1[1] = mfma(k1t[kt + unit_of(M, r, 0) + 32 * K1T_STR], h2[M][r], d1[1]);
             }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
@@ -385,7 +376,7 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
 #pragma unroll
         for (int M = 0; M < 2; ++M)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) stage[wr + UNIT(M, r) * STR] = h1[M][r] > 0.0f ? d1[M][r] : 0.0f;
+            for (int r = 0; r < 16; ++r) stage[wr + unit_of(M, r, 0) * STR] = h1[M][r] > 0.0f ? d1[M][r] : 0.0f;
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
         {
@@ -429,14 +420,14 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     // the first wavefront stores, the others add
-                    const int p1 = q1 + static_cast<int>(UNIT(M, r)) * HID;
+                    const int p1 = q1 + unit_of(M, r, 0) * HID;
                     red[p1] = w == 0 ? acc1[M][0][r] : red[p1] + acc1[M][0][r];
                     red[p1 + 32] = w == 0 ? acc1[M][1][r] : red[p1 + 32] + acc1[M][1][r];
                 }
         }
         __syncthreads();
     }
-    // the small sums, straight from their slots: register 16 M + r of a lane is unit UNIT(M, r) + 4 h
+    // the small sums, straight from their slots: register 16 M + r of a lane is unit unit_of(M, r, 0) + 4 h
     for (int i = tid; i < 32 * SMALL_SLOTS; i += BLOCK) {
         const int reg = i / SMALL_SLOTS, slot = i - reg * SMALL_SLOTS;
         const int u = 32 * (reg >> 4) + (reg & 3) + 8 * ((reg & 15) >> 2);
@@ -548,33 +539,6 @@ __global__ __launch_bounds__(APPLY_BLOCK) void lrn_apply_kernel(const ApplyArgs 
 }
 
 // ------------------------------------------------------------------ host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* what)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return static_cast<int>(e);
-}
-
-// NaN and infinity by their bits: the library is built with -fno-honor-nans, which lets the compiler drop x != x
-bool is_number(double x)
-{
-    uint64_t bits;
-    std::memcpy(&bits, &x, sizeof(bits));
-    return ((bits >> 52) & 0x7FFu) != 0x7FFu;
-}
-
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // the launch shape: functions of B alone
 struct Shape {
     int64_t tiles;

@@ -17,24 +17,20 @@
 
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 
 #include "../../include/aqua_policy.h"
 #include "aqua_device.hpp"
+#include "aqua_host.hpp"
+#include "aqua_qnet.hpp"
 
 namespace {
 
 using aqua::draw;
 using aqua::u_01;
+using namespace aqua::qnet;
 
-constexpr uint32_t STREAM_POLICY = AQUAPOL_STREAM;      // aqua_device.hpp: 0, 1, 3, 4 are the environment's
-static_assert(STREAM_POLICY != aqua::STREAM_STEP && STREAM_POLICY != aqua::STREAM_PLACE && STREAM_POLICY != aqua::STREAM_POSE &&
-              STREAM_POLICY != aqua::STREAM_ACT, "the policy draws need a stream of their own");
-
-constexpr int IN = AQUAPOL_INPUTS, HID = AQUAPOL_HIDDEN, ACT = AQUAPOL_ACTIONS;
-constexpr int TILE = 32;                 // worlds per wavefront and pass: the MFMA's column count
+static_assert(STREAM_POLICY == AQUAPOL_STREAM, "aqua_policy.h names the stream of the policy draws");
+static_assert(IN == AQUAPOL_INPUTS && HID == AQUAPOL_HIDDEN && ACT == AQUAPOL_ACTIONS, "aqua_policy.h names the network's sizes");
 constexpr int K1_STEPS = 3;              // layer 1: K = 5 padded to 6 (the sixth weight and input are zero)
 constexpr int K2_STEPS = HID / 2;        // layer 2: 32 k-steps of 2 for each of the two row blocks
 constexpr int BLOCK = 256, WAVES = BLOCK / 64;
@@ -54,11 +50,6 @@ constexpr int LDS_B2 = LDS_K2 + 2 * ACT * 32;               // [ACT] + 1 pad
 constexpr int LDS_FLOATS = LDS_B2 + 4;
 constexpr int BLOB_FLOATS = OFF_LDS + LDS_FLOATS;
 static_assert(OFF_LDS % 4 == 0 && LDS_FLOATS % 4 == 0, "the LDS part is copied as float4");
-
-// the unit (row of the accumulator tile) that register r of row block M holds on lane half h
-__host__ __device__ constexpr int unit_of(int M, int r, int h) { return 32 * M + (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PolicyArgs {
     const float* blob;
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qpolicy_kernel(const Po
             if constexpr (EPS) {
                 uint32_t r[4];
                 draw(a.seed, static_cast<uint64_t>(a.env_offset + i), tick, STREAM_POLICY, 0, r);
-                if (u_01(r[0]) < a.epsilon) act = static_cast<int>(((r[1] >> 8) * 3u) >> 24);
+                if (u_01(r[0]) < a.epsilon) act = static_cast<int>(random_action(r));
             }
             if (a.action != nullptr) a.action[i] = static_cast<uint8_t>(act);
             if (a.q != nullptr) {
@@ -202,25 +193,6 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qpolicy_kernel(const Po
 }
 
 // ------------------------------------------------------------------ host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* what)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return static_cast<int>(e);
-}
-
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // compute units of a device, asked once (an attribute query is no stream operation: legal under capture)
 constexpr int MAX_DEVICES = 64;
 std::atomic<int> g_cus[MAX_DEVICES];

@@ -4,7 +4,6 @@ touching a device, sizes its workspace monotonically, has no CPU path; the numpy
 itself checked against a per-world loop written the way main/impl/dqn.py:151-186 reads; and the compiled kernels have no
 scratch, no spills and no floating-point atomics."""
 import ctypes
-import importlib.util
 import os
 import re
 import types
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import _episodes as E
+from tests import _isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 0x10000            # a "device pointer" for calls that must fail (or return) before anything dereferences it
@@ -34,10 +34,7 @@ def ecapi():
 
 @pytest.fixture(scope="module")
 def isa():
-    spec = importlib.util.spec_from_file_location("episodes_isa", os.path.join(ROOT, "tools", "episodes_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.kernels(mod.listing())
+    return _isa.kernels("episodes")
 
 
 def test_library_builds_loads_and_exports_its_header(ecapi):

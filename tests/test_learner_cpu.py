@@ -3,13 +3,13 @@ what its header declares and leaves the other two libraries' interfaces alone, r
 device, sizes its workspace monotonically, finds the blob permutation from aquapol_pack_weights, has no CPU path, and its
 compiled kernels keep the weight gradients on v_mfma_f32_32x32x2_f32 without scratch or spills."""
 import ctypes
-import importlib.util
 import os
 import re
 
 import numpy as np
 import pytest
 
+from tests import _isa
 from tests import _learner as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,10 +26,7 @@ def lcapi():
 
 @pytest.fixture(scope="module")
 def isa():
-    spec = importlib.util.spec_from_file_location("learner_isa", os.path.join(ROOT, "tools", "learner_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.kernels(mod.listing())
+    return _isa.kernels("learner")
 
 
 def test_library_builds_loads_and_exports_its_header(lcapi):

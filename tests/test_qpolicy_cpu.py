@@ -4,13 +4,14 @@ packs weights deterministically in the layout the kernel's MFMA orientation need
 the compiled kernel keeps the 64 x 64 layer on v_mfma_f32_32x32x2_f32 without scratch or spills."""
 import ctypes
 import hashlib
-import importlib.util
 import json
 import os
 import re
 
 import numpy as np
 import pytest
+
+from tests import _isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 0x10000            # a "device pointer" for calls that must fail (or return) before anything dereferences it
@@ -27,10 +28,7 @@ def pcapi():
 
 @pytest.fixture(scope="module")
 def isa():
-    spec = importlib.util.spec_from_file_location("make_policy_isa_budget", os.path.join(ROOT, "tools", "make_policy_isa_budget.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    return _isa.kernels("policy")
 
 
 def _int_layers():
@@ -196,7 +194,7 @@ def test_argument_validation_without_touching_a_device(pcapi):
 
 
 def test_codegen_keeps_the_hidden_layer_on_the_f32_mfma_without_scratch(isa):
-    ks = isa.kernels(isa.listing())
+    ks = isa
     assert len(ks) == 4, sorted(ks)                    # raw / normalised input x greedy / epsilon-greedy
     counts = {}
     for name, k in ks.items():

@@ -4,54 +4,14 @@ aquaticgymenv_amd/csrc/aqua_learner.hip device-only with the library's flags and
 spills, LDS, occupancy and the static count of v_mfma_f32_32x32x2_f32.  tests/test_learner_cpu.py gates the same listing.
 """
 import json
-import os
 import re
-import subprocess
-import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def listing():
-    """-> the device assembly of aqua_learner.hip as text"""
-    from aquaticgymenv_amd import build
-    flags = [f for f in build.LEARNER_FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "aqua_learner.s")
-        subprocess.check_call([build.hipcc_path(), *flags, "--cuda-device-only", "-S", "-o", out, *build.LEARNER_SRC],
-                              stderr=subprocess.DEVNULL)
-        return open(out).read()
-
-
-def kernels(text):
-    """-> {mangled name: {"body": str, "meta": {key: int}, "stats": {key: int}}} for every kernel of the code object"""
-    names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
-    out = {}
-    for name in names:
-        m = re.search(r"^%s:[^\n]*\n(.*?)\n\s*s_endpgm" % re.escape(name), text, re.M | re.S)
-        out[name] = {"body": m.group(1), "meta": {}, "stats": {}}
-        tail = text[m.start():]
-        for key in ("NumVgprs", "NumAgprs", "TotalNumVgprs", "NumSgprs", "ScratchSize", "Occupancy", "LDSByteSize"):
-            mm = re.search(r"^; %s: (\d+)" % key, tail, re.M)
-            if mm:
-                out[name]["stats"][key] = int(mm.group(1))
-    for block in re.split(r"\n  - \.agpr_count:", text)[1:]:
-        mm = re.search(r"\.name:\s+(\S+)", block)
-        if mm and mm.group(1) in out:
-            block = ".agpr_count:" + block
-            for key in ("agpr_count", "vgpr_count", "sgpr_count", "private_segment_fixed_size", "sgpr_spill_count",
-                        "vgpr_spill_count", "group_segment_fixed_size"):
-                m2 = re.search(r"\.%s:\s+(\d+)" % key, block)
-                if m2:
-                    out[mm.group(1)]["meta"][key] = int(m2.group(1))
-    return out
+from isa_listing import kernels, listing
 
 
 def main():
     rows = {}
-    for name, k in sorted(kernels(listing()).items()):
+    for name, k in sorted(kernels(listing("learner")).items()):
         rows[name] = dict(k["meta"], occupancy_waves_per_simd=k["stats"].get("Occupancy"),
                           mfma_f32_32x32x2_f32=len(re.findall(r"\bv_mfma_f32_32x32x2_f32\b", k["body"])),
                           instructions=len(re.findall(r"^\s+[a-z]\w+", k["body"], re.M)))
