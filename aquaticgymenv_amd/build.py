@@ -38,6 +38,21 @@ LIBRARIES = {
     "learner": _library("learner", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
     "episodes": _library("episodes", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
 }
+# Libraries added since, in build order behind the four above (whose table, order and command lines are pinned).
+# render: render(mode="rgb_array") frames and the thrust / ICC overlay (include/aqua_render.h).
+EXTRA_LIBRARIES = {
+    "render": _library("render", ["aqua_device.hpp", "aqua_host.hpp"]),
+}
+
+
+def library(name):
+    """the table entry of library `name`, from LIBRARIES or EXTRA_LIBRARIES"""
+    return LIBRARIES[name] if name in LIBRARIES else EXTRA_LIBRARIES[name]
+
+
+def all_libraries():
+    """every library's name, in build order"""
+    return list(LIBRARIES) + list(EXTRA_LIBRARIES)
 
 
 def hipcc_path():
@@ -48,7 +63,7 @@ def hipcc_path():
 
 
 def needs_build(name="hip"):
-    entry = LIBRARIES[name]
+    entry = library(name)
     if not os.path.exists(entry["lib"]):
         return True
     t = os.path.getmtime(entry["lib"])
@@ -57,13 +72,13 @@ def needs_build(name="hip"):
 
 def build_command(name, extra_flags=()):
     """the hipcc command line of build_library(name), without running it"""
-    entry = LIBRARIES[name]
+    entry = library(name)
     return [hipcc_path(), *entry["flags"], "-Wall", "-Wno-unused-function", *extra_flags, "-o", entry["lib"] + ".tmp", *entry["src"]]
 
 
 def build_library(name, force=False, verbose=False, extra_flags=()):
     """Compile the library's source -> lib/libaqua_<name>.so for gfx950.  Returns the library path."""
-    lib = LIBRARIES[name]["lib"]
+    lib = library(name)["lib"]
     if not force and not needs_build(name):
         return lib
     os.makedirs(os.path.dirname(lib), exist_ok=True)
@@ -82,6 +97,8 @@ LEARNER_SRC, LEARNER_DEPS, LEARNER_LIB, LEARNER_FLAGS = (LIBRARIES["learner"][k]
 EPISODES_SRC, EPISODES_DEPS, EPISODES_LIB, EPISODES_FLAGS = (LIBRARIES["episodes"][k] for k in ("src", "deps", "lib", "flags"))
 build_hip, build_policy, build_learner, build_episodes = (functools.partial(build_library, n) for n in LIBRARIES)
 policy_needs_build, learner_needs_build, episodes_needs_build = (functools.partial(needs_build, n) for n in ("policy", "learner", "episodes"))
+RENDER_SRC, RENDER_DEPS, RENDER_LIB, RENDER_FLAGS = (EXTRA_LIBRARIES["render"][k] for k in ("src", "deps", "lib", "flags"))
+build_render, render_needs_build = functools.partial(build_library, "render"), functools.partial(needs_build, "render")
 
 
 def build_variant(name, flags, verbose=False):
@@ -131,5 +148,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in LIBRARIES:
+    for name in all_libraries():
         print(build_library(name, force="--force" in sys.argv, verbose=True))

@@ -75,7 +75,7 @@ class _LazyInfo(dict):
 
 
 class AquaEnv(_EnvBase):
-    metadata = {"render.modes": ["human"]}
+    metadata = {"render.modes": ["human", "rgb_array"]}
     continuous = False
 
     def __init__(self, obstacles=False, waves=True, random_boat=True, random_goal=True, num_envs=1, device=None,
@@ -110,6 +110,7 @@ class AquaEnv(_EnvBase):
                                 random_goal=random_goal, continuous=self.continuous, device=device, seed=seed,
                                 auto_reset=autoreset if self.num_envs > 1 else False)
         self._needs_reset = True
+        self._renderer = None             # a FrameRenderer from the first render("rgb_array") on
 
     # ------------------------------------------------------------------ reference-shaped API
     @property
@@ -134,8 +135,25 @@ class AquaEnv(_EnvBase):
             raise RuntimeError("call reset() before step()")
         if self.num_envs == 1:
             return self._step_single(action)
+        if self._renderer is not None:
+            self._record(action)
         obs, reward, term = self.core.step(action)
         return obs, reward, term != 0, _LazyInfo(term)
+
+    def _record(self, action):
+        """Hand the renderer the action of the step about to be taken, in the layout it records from.  A uint8 device
+        tensor (discrete) is recorded as it is; any other index is folded the way the step kernels fold it (-3..-1 wrap as
+        the reference's list lookup does, aqua.py:154, the rest clamps to 0..2), which costs a small tensor per step."""
+        torch = self.core.torch
+        a = action if isinstance(action, torch.Tensor) else torch.as_tensor(np.asarray(action))
+        a = a.to(self.core.device)
+        if self.continuous:
+            a = a.to(torch.float32).reshape(self.num_envs, 2)
+            a = torch.stack([a[:, 0], a[:, 1]])       # [2][N], rows contiguous
+        elif a.dtype != torch.uint8 or a.dim() != 1:
+            a = a.reshape(-1).to(torch.int64)
+            a = torch.where(a < 0, a + 3, a).clamp_(0, 2).to(torch.uint8)
+        self._renderer.before_step(a)
 
     def _step_single(self, action):
         if self.continuous:
@@ -152,6 +170,8 @@ class AquaEnv(_EnvBase):
             if not -3 <= idx < 3:
                 raise IndexError("list index out of range")      # what self.actions[action] raises (aqua.py:154)
             act = np.array([idx], dtype=np.int64)
+        if self._renderer is not None:
+            self._record(act % 3 if not self.continuous else act)
         obs, reward, term = self.core.step(act)
         host = self.core.torch.cat([obs[0], reward[:1], term[:1].to(obs.dtype)]).to("cpu").numpy()
         code = int(host[6])
@@ -162,11 +182,25 @@ class AquaEnv(_EnvBase):
             rew = 10 if code == 3 else -10
         return host[0:5].astype(np.float64), rew, code != 0, info
 
-    def render(self, mode="human"):
-        raise NotImplementedError("rendering (aqua.py:215-371, a pyglet viewer) is outside the batched step() path")
+    def render(self, mode="human", worlds=None):
+        """mode="rgb_array": the frame(s) of aqua.py:215-365 drawn on the device, 500 x 500 x 3 uint8 (view_scale 5):
+        num_envs == 1 -> a numpy array; otherwise the device tensor [M, 500, 500, 3] of worlds[...] (an int32 device
+        tensor), by default of the first min(num_envs, 16) worlds.  From the first such call on, step() records thrusts
+        and ICC for the next frame.  Only step() records: after rollout(), or a step taken on env.core directly, the
+        frame shows the new pose with the bars and the ICC of the last step() (none before the first).
+        mode="human" (the pyglet window) is not provided."""
+        if mode != "rgb_array":
+            raise NotImplementedError("rendering (aqua.py:215-371, a pyglet viewer) is outside the batched step() path")
+        if self._renderer is None:
+            from aquaticgymenv_amd.render import FrameRenderer
+            self._renderer = FrameRenderer(self.core, size=500)
+        frames = self._renderer.render(worlds=worlds)
+        if self.num_envs == 1:
+            return frames[0].to("cpu").numpy()
+        return frames
 
     def close(self):
-        pass
+        self._renderer = None
 
     # ------------------------------------------------------------------ batch extras
     def rollout(self, steps, actions=None, fused=False, keep_all=True):

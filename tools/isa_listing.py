@@ -14,9 +14,9 @@ if ROOT not in sys.path:
 
 
 def listing(name):
-    """-> the device assembly of library `name` of aquaticgymenv_amd.build.LIBRARIES as text, compiled with the library's flags"""
+    """-> the device assembly of library `name` of aquaticgymenv_amd.build (LIBRARIES or EXTRA_LIBRARIES) as text, compiled with the library's flags"""
     from aquaticgymenv_amd import build
-    entry = build.LIBRARIES[name]
+    entry = build.library(name)
     flags = [f for f in entry["flags"] if f not in ("-shared", "-fPIC")]
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "aqua_%s.s" % name)
