@@ -43,16 +43,29 @@ LIBRARIES = {
 EXTRA_LIBRARIES = {
     "render": _library("render", ["aqua_device.hpp", "aqua_host.hpp"]),
 }
+# Libraries behind those (both tables above and what all_libraries() returns are pinned too).
+# replay: the experience ring with its cursor and size on the device (include/aqua_replay.h).
+ADDON_LIBRARIES = {
+    "replay": _library("replay", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
 
 
 def library(name):
-    """the table entry of library `name`, from LIBRARIES or EXTRA_LIBRARIES"""
-    return LIBRARIES[name] if name in LIBRARIES else EXTRA_LIBRARIES[name]
+    """the table entry of library `name`, from LIBRARIES, EXTRA_LIBRARIES or ADDON_LIBRARIES"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES):
+        if name in table:
+            return table[name]
+    return ADDON_LIBRARIES[name]
 
 
 def all_libraries():
     """every library's name, in build order"""
     return list(LIBRARIES) + list(EXTRA_LIBRARIES)
+
+
+def every_library():
+    """every library's name, the add-ons included, in build order (what build() and `python -m` compile)"""
+    return all_libraries() + list(ADDON_LIBRARIES)
 
 
 def hipcc_path():
@@ -99,6 +112,8 @@ build_hip, build_policy, build_learner, build_episodes = (functools.partial(buil
 policy_needs_build, learner_needs_build, episodes_needs_build = (functools.partial(needs_build, n) for n in ("policy", "learner", "episodes"))
 RENDER_SRC, RENDER_DEPS, RENDER_LIB, RENDER_FLAGS = (EXTRA_LIBRARIES["render"][k] for k in ("src", "deps", "lib", "flags"))
 build_render, render_needs_build = functools.partial(build_library, "render"), functools.partial(needs_build, "render")
+REPLAY_SRC, REPLAY_DEPS, REPLAY_LIB, REPLAY_FLAGS = (ADDON_LIBRARIES["replay"][k] for k in ("src", "deps", "lib", "flags"))
+build_replay, replay_needs_build = functools.partial(build_library, "replay"), functools.partial(needs_build, "replay")
 
 
 def build_variant(name, flags, verbose=False):
@@ -148,5 +163,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in all_libraries():
+    for name in every_library():
         print(build_library(name, force="--force" in sys.argv, verbose=True))

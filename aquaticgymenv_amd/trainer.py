@@ -1,0 +1,159 @@
+"""DQNLoop: one iteration of the reference's training loop (main/impl/dqn.py:147-184) as ONE chain of launches on one
+stream, and that chain captured into one HIP graph.
+
+Every stage already lives on the device -- the Q-network policy (qpolicy.py), the exploration pass and the episode
+accounting (episodes.py), the step kernels (batched.py), the learner (learner.py) -- and each is capturable by itself.  What
+kept the whole iteration out of a graph was the experience ring's cursor and size, Python integers of ReplayRing;
+DeviceReplayRing (replay.py) keeps them in device memory.  An iteration is then, in stream order:
+
+    1. greedy policy launch, keyed by the device tick base      6. tracker.after_step()         (two launches)
+    2. tracker.explore(tick_base=...)                           7. ring draw: idx of the update t -> t + 1
+    3. ring open: (s, a, ok)                                    8. learner.update(view, B, idx=idx)  (two launches)
+    4. step launch                                              9. tick advance
+    5. ring close: (r, s', d), cursor and size move on
+
+step() queues exactly that eagerly; capture() records the same calls once and launch() replays them: eleven kernels, no
+host work between them.  Both give, bit for bit, what examples/dqn_train.py --eager computes with ReplayRing and
+learner.update(ring, B).  There is no CPU path.
+"""
+import ctypes
+
+from . import _capi, _learner_capi
+from .batched import RolloutGraph
+
+
+class DQNLoop(object):
+    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64):
+        """env: a BatchedAqua of discrete actions with normalized_obs=True; qnet: the acting QNetwork; learner: the DQNLearner
+        that trains it; ring: a DeviceReplayRing of env; tracker: an EpisodeTracker of env with an epsilon schedule.
+        Everything on one device; anything else is a ValueError."""
+        if env.continuous:
+            raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
+        if env.obs_norm_buf is None:
+            raise ValueError("the ring stores the normalised observation: construct the env with normalized_obs=True")
+        if not getattr(qnet, "_aquapol_network", False):
+            raise ValueError("expected a QNetwork")
+        if learner.qnet is not qnet:
+            raise ValueError("the learner trains another network than the one that acts")
+        if getattr(ring, "header", None) is None or ring.env is not env:
+            raise ValueError("expected a DeviceReplayRing of this env")
+        if tracker.env is not env or tracker.epsilon is None:
+            raise ValueError("expected an EpisodeTracker of this env with epsilon=(init, final, decay)")
+        for what, dev in (("network", qnet.device), ("learner", learner.device), ("ring", ring.device), ("tracker", tracker.device)):
+            if dev != env.device:
+                raise ValueError("the environment is on %s, the %s on %s" % (env.device, what, dev))
+        B = int(batch_size)
+        if B < 1 or B > _learner_capi.MAX_BATCH:
+            raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _learner_capi.MAX_BATCH))
+        self.env, self.qnet, self.learner, self.ring, self.tracker, self.batch_size = env, qnet, learner, ring, tracker, B
+        self.torch = env.torch
+        self.view = ring.learner_view()
+        self.idx = self.torch.full((B,), -1, dtype=self.torch.int32, device=env.device)
+        env.policy_action                                     # (allocated here, not inside a capture)
+        learner._grow(B)
+
+    # ------------------------------------------------------------------ the iteration
+    def _queue(self):
+        """the nine stages on torch's current stream, every draw keyed by the device tick base"""
+        from . import _policy_capi
+        env, ring, tracker = self.env, self.ring, self.tracker
+        action, tb = env.policy_action, env._tick_dev
+        s = env._stream()
+        _policy_capi.check(env._policy_launch(self.qnet, 0.0, 0, tb.data_ptr(), s), "aquapol_act_f32")
+        tracker.explore(action, tick=0, tick_base=tb)
+        ring.before_step(action)
+        _capi.check(env._step_launch(action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
+                                     env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
+        ring.after_step()
+        tracker.after_step()
+        ring.draw(self.batch_size, self.learner, out=self.idx)
+        self.learner.update(self.view, self.batch_size, idx=self.idx)
+        _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
+
+    def step(self):
+        """Queue one iteration eagerly -> (reward, term) of its step, as env.step() returns them"""
+        env = self.env
+        with self.torch.cuda.device(env.device):
+            env._sync_device_tick()
+            self._queue()
+        env._tick += 1
+        env._device_tick += 1
+        return env.reward[:env.num_envs], env.term[:env.num_envs]
+
+    # ------------------------------------------------------------------ the graph
+    def _warm_up(self):
+        """Every kernel of the iteration runs once, on the current stream, and leaves no trace: the kernels' code is on the
+        device before the capture begins.  The policy writes policy_action (an output); the exploration pass works on a
+        scratch row; the accounting sees a batch in which no world counts; the ring kernels run on a one-slot scratch ring;
+        the learner gets a minibatch without a sample (documented to leave everything as it was); the step is taken on a
+        snapshot and taken back."""
+        from . import _policy_capi
+        torch, env, tracker, learner = self.torch, self.env, self.tracker, self.learner
+        dev, n = env.device, env.num_envs
+        rpl = self.ring._capi
+        s = env._stream()
+        tb = env._tick_dev
+        _policy_capi.check(env._policy_launch(self.qnet, 0.0, 0, tb.data_ptr(), s), "aquapol_act_f32")
+        tracker.explore(torch.zeros(env.ld, dtype=torch.uint8, device=dev), tick=0, tick_base=tb)
+        tracker.after_step(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
+                           torch.full((n,), -1, dtype=torch.int32, device=dev))
+        header = torch.zeros(rpl.HEADER_WORDS, dtype=torch.int64, device=dev)
+        rows = torch.zeros((5, 1), dtype=torch.float32, device=dev)
+        f32, u8 = torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.uint8, device=dev)
+        idx = torch.full((self.batch_size,), -1, dtype=torch.int32, device=dev)
+        rpl.check(rpl.lib.aquarpl_open(header.data_ptr(), rows.data_ptr(), u8[0:].data_ptr(), u8[1:].data_ptr(), 1, 1, rows.data_ptr(), 1,
+                                       u8[2:].data_ptr(), rpl.ACT_U8, 1, None, 1, s), "aquarpl_open")
+        rpl.check(rpl.lib.aquarpl_close(header.data_ptr(), f32.data_ptr(), rows.data_ptr(), u8[0:].data_ptr(), 1, 1, f32.data_ptr(),
+                                        rows.data_ptr(), 1, u8[2:].data_ptr(), 1, s), "aquarpl_close")
+        rpl.check(rpl.lib.aquarpl_draw(header.data_ptr(), u8[1:].data_ptr(), 1, learner.t.data_ptr(), learner.seed, idx.data_ptr(),
+                                       self.batch_size, s), "aquarpl_draw")
+        idx.fill_(-1)
+        loss = learner.loss.clone()
+        grad = learner.grad.clone()
+        learner.update(self.view, self.batch_size, idx=idx)                  # no sample: nothing but loss and grad is written
+        learner.loss.copy_(loss)
+        learner.grad.copy_(grad)
+        snap = env.snapshot()
+        _capi.check(env._step_launch(env.policy_action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
+                                     env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
+        env.restore(snap)
+        _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 0, s), "aqua_tick_advance")
+        torch.cuda.current_stream(dev).synchronize()
+
+    def capture(self):
+        """-> a RolloutGraph whose launch() replays one iteration: the nine stages as ONE chain of eleven kernel nodes (no
+        parallel branches).  It reads and advances the device state only -- tick base, epsilon, ring header, Adam's t -- so
+        every replay acts, explores, appends, draws and learns afresh; qnet.load() or learner.load_state_dict() between
+        replays takes effect on the next one.  The learner's workspace is grown and every kernel has run before the capture."""
+        torch, env, lib = self.torch, self.env, _capi.lib
+        with torch.cuda.device(env.device):
+            env._sync_device_tick()
+            self._warm_up()
+            env._sync_device_tick()
+            cap = torch.cuda.Stream(device=env.device)
+            cap.wait_stream(torch.cuda.current_stream(env.device))
+            handle = ctypes.c_void_p()
+            was_open = self.ring._open
+            try:
+                with torch.cuda.stream(cap):
+                    s = env._stream()
+                    _capi.check(lib.aqua_graph_begin(s), "aqua_graph_begin")
+                    error = None
+                    try:
+                        self._queue()
+                    except Exception as exc:              # the capture must be ended before anything else happens
+                        error = exc
+                    rc_end = lib.aqua_graph_end(s, ctypes.byref(handle))
+                    if error is not None:
+                        if rc_end == 0:
+                            lib.aqua_graph_destroy(handle)
+                        self.ring._open = was_open
+                        raise error
+                    _capi.check(rc_end, "aqua_graph_end")
+            finally:
+                torch.cuda.current_stream(env.device).wait_stream(cap)
+        g = RolloutGraph(env, handle, 1, env.reward, env.term)
+        g._actions = (self.qnet, env.policy_action)
+        g._loop = self                                        # the buffers the graph's nodes point at
+        g.done_history = None
+        return g

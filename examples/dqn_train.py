@@ -10,7 +10,11 @@ epsilon, which decays once per finished episode as dqn.py:184 does and is read b
 Every 100 steps the line of dqn.py:194-200 is printed from the tracker -- mean return, mean length and success rate of the
 last 100 episodes, epsilon; that print is the only host read of the loop.
 
-    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles]
+By default the whole iteration -- act, explore, record, step, record, account, draw, update -- is ONE captured graph
+(trainer.DQNLoop over a DeviceReplayRing, whose cursor and size live on the device): one launch from Python per iteration
+instead of about sixteen.  --eager keeps the loop written out call by call with ReplayRing; both compute the same bits.
+
+    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager]
 """
 import argparse
 import os
@@ -24,7 +28,8 @@ from aquaticgymenv_amd.batched import BatchedAqua
 from aquaticgymenv_amd.episodes import EpisodeTracker
 from aquaticgymenv_amd.learner import DQNLearner
 from aquaticgymenv_amd.qpolicy import QNetwork
-from aquaticgymenv_amd.replay import ReplayRing
+from aquaticgymenv_amd.replay import DeviceReplayRing, ReplayRing
+from aquaticgymenv_amd.trainer import DQNLoop
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=1024)
@@ -34,6 +39,7 @@ ap.add_argument("--buffer", type=int, default=1 << 20, help="ring capacity in tr
 ap.add_argument("--obstacles", action="store_true")
 ap.add_argument("--epsilon-decay", type=float, default=10000, help="a factor, or the number of episodes to reach the final epsilon")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--eager", action="store_true", help="issue every launch of the iteration from Python (ReplayRing) instead of replaying one graph")
 args = ap.parse_args()
 
 # default_hyperparam of dqn.py
@@ -49,22 +55,26 @@ learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref",
 
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()
-ring = ReplayRing(env, capacity=max(args.buffer, args.envs))
+ring = (ReplayRing if args.eager else DeviceReplayRing)(env, capacity=max(args.buffer, args.envs))
 tracker = EpisodeTracker(env, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))     # decay >= 1: episodes to reach EPS_FINAL
+graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch).capture()
 for step in range(1, args.steps + 1):
-    # env.step(policy=qnet, epsilon=...) in three calls: greedy actions, the exploring draws under the device epsilon, and
-    # the step, so that the ring sees the action before the step
-    action = qnet.act(env, epsilon=0.0, out=env.policy_action)
-    tracker.explore(env.policy_action)
-    ring.before_step(env.policy_action)
-    obs, reward, term = env.step(action)
-    ring.after_step()
-    tracker.after_step()                                       # returns, lengths, the log, epsilon: all on the device
-    learner.update(ring, args.batch)                           # minibatch drawn on the device; qnet acts with the new weights
+    if graph is not None:
+        graph.launch()                                         # the nine stages below and the tick advance, as one graph
+    else:
+        # env.step(policy=qnet, epsilon=...) in three calls: greedy actions, the exploring draws under the device epsilon, and
+        # the step, so that the ring sees the action before the step
+        action = qnet.act(env, epsilon=0.0, out=env.policy_action)
+        tracker.explore(env.policy_action)
+        ring.before_step(env.policy_action)
+        obs, reward, term = env.step(action)
+        ring.after_step()
+        tracker.after_step()                                   # returns, lengths, the log, epsilon: all on the device
+        learner.update(ring, args.batch)                       # minibatch drawn on the device; qnet acts with the new weights
     if step % 100 == 0:                                        # the only host reads of the loop
         c, last = tracker.counts(), tracker.last(100)
         k = max(len(last["ret"]), 1)
         print("step %6d  episodes %7d  mean_last_100: reward %8.2f  steps %6.1f  success %3.0f %%  loss %10.4f  epsilon %.3f  ring %d" %
               (step, c["episodes"], float(last["ret"].sum()) / k, float(last["len"].sum()) / k,
-               100.0 * float((last["code"] == 3).sum()) / k, float(learner.loss), float(tracker.epsilon), ring.size))
+               100.0 * float((last["code"] == 3).sum()) / k, float(learner.loss), float(tracker.epsilon), ring.size if args.eager else ring.filled()))
 learner.weights()                                              # qnet.layers now holds the trained network
