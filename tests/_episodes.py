@@ -82,6 +82,27 @@ def draws(oracle, n, seed, env_offset, tick):
     return u, (((r[:, 1] >> np.uint64(8)) * np.uint64(3)) >> np.uint64(24)).astype(np.uint8)
 
 
+def draws_vectorised(n, seed, env_offset, tick):
+    """draws() for worlds env_offset .. env_offset + n - 1 at once, through tests/_placement.py's array Philox (stream 5,
+    attempt 0) -> (the uniform float32 [n], the exploring action uint8 [n])"""
+    from tests import _placement as P
+    r = P.draw(seed, env_offset + np.arange(n, dtype=np.int64), tick, STREAM, 0)
+    u = (r[0] >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return u, (((r[1] >> np.uint64(8)) * np.uint64(3)) >> np.uint64(24)).astype(np.uint8)
+
+
+BLOCK, MAX_BLOCKS, EXPLORE_MAX_BLOCKS = 256, 1024, 2048    # csrc/aqua_episodes.hip
+
+
+def launch_shape(N):
+    """csrc/aqua_episodes.hip's shape_of restated: -> (chunk, blocks).  Block b accounts worlds [b chunk, (b + 1) chunk), a
+    tile of BLOCK worlds per trip.  tests/test_launch_regimes_cpu.py pins BLOCK and MAX_BLOCKS through
+    aquaep_workspace_bytes."""
+    tiles = (N + BLOCK - 1) // BLOCK
+    chunk = max(1, (tiles + MAX_BLOCKS - 1) // MAX_BLOCKS) * BLOCK
+    return chunk, (N + chunk - 1) // chunk
+
+
 def explore(action, eps, u, drawn):
     """the exploration pass on a numpy uint8 action array -> (the new actions, which worlds explored)"""
     return np.where(u < np.float32(eps), drawn, action).astype(np.uint8), u < np.float32(eps)

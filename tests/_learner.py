@@ -13,6 +13,16 @@ SHAPES = ((5, 64), (64, 64), (64, 3))
 STRATEGIES = ("double_ref", "double", "fixed", "standard")
 STREAM = 6
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-7
+TILE, WAVES, GMAX = 32, 2, 512     # samples per tile, wavefronts per workgroup, workgroups at most (csrc/aqua_learner.hip)
+
+
+def launch_shape(B):
+    """csrc/aqua_learner.hip's shape_of restated: -> (tiles, tiles_per_wave, groups).  Wavefront w of group g takes tiles
+    (g WAVES + w) tiles_per_wave .. + tiles_per_wave - 1.  tests/test_launch_regimes_cpu.py pins GMAX through
+    aqualrn_workspace_bytes."""
+    tiles = (B + TILE - 1) // TILE
+    tpw = max(1, (tiles + WAVES * GMAX - 1) // (WAVES * GMAX))
+    return tiles, tpw, (tiles + WAVES * tpw - 1) // (WAVES * tpw)
 
 
 def flatten(layers):
@@ -187,6 +197,101 @@ def int_ring(cap, size, seed, bad_ok=0.0):
     ring["r"][size:] = 3.0e30
     ring["ok"][size:] = 1
     return ring
+
+
+VALID_MAX = 4096                   # samples other than -1 in a sparse batch: keeps every integer sum below 2^24
+
+
+def wave_span(B, W, first, last=None):
+    """the samples [lo, hi) of tiles `first` .. `last` (counted inside the wavefront) of wavefront W = group * WAVES + wave"""
+    tpw = launch_shape(B)[1]
+    last = first if last is None else last
+    return min(B, TILE * (W * tpw + first)), min(B, TILE * (W * tpw + last + 1))
+
+
+def sparse_indices(B, ring, cap, seed):
+    """An index vector for a batch whose wavefronts take several tiles each, with at most VALID_MAX entries other than -1,
+    placed by launch_shape(B): -> (idx int64 [B], plan).  plan names the wavefronts check_sparse() then looks at:
+      full    wavefronts whose every sample is a live slot: both of the last group, and wavefront 0 of group 0 unless one
+              wavefront alone is a quarter of VALID_MAX (then the last wavefront of the last group only)
+      spread  wavefront 1: a few live samples in its tiles 0, 1 and tiles_per_wave - 1, nothing else
+      late    wavefront 3: nothing in its first tile; its second holds the invalid kinds and the duplicate of
+              tests/test_learner_gpu.py::_mixed_indices
+      mid     both wavefronts of the middle group, every tile partly filled with any slot below size (ok == 0 among them)
+    and 2 400 samples (1 000 where a wavefront has more than four tiles) are scattered over the whole batch."""
+    tiles, tpw, groups = launch_shape(B)
+    assert tpw >= 2 and groups >= 8, (B, tpw, groups)
+    rng = np.random.RandomState(seed)
+    size = int(ring["size"])
+    live = np.nonzero(ring["ok"][:size] != 0)[0]
+    dead = np.nonzero(ring["ok"][:size] == 0)[0]
+    idx = np.full(B, -1, dtype=np.int64)
+    at = rng.choice(B, 2400 if tpw <= 4 else 1000, replace=False)
+    idx[at] = rng.randint(0, size, at.size)
+    last = groups - 1
+    full = [W for W in (WAVES * last, WAVES * last + 1) if wave_span(B, W, 0)[0] < B]
+    full = full[-1:] if 4 * tpw * TILE >= VALID_MAX else [0] + full
+    for W in full:
+        lo, hi = wave_span(B, W, 0, tpw - 1)
+        idx[lo:hi] = live[rng.randint(0, live.size, hi - lo)]
+    for it in sorted({0, 1, tpw - 1}):
+        lo, hi = wave_span(B, 1, it)
+        idx[lo:hi] = -1
+        idx[lo + rng.choice(hi - lo, 5, replace=False)] = live[rng.randint(0, live.size, 5)]
+    lo, hi = wave_span(B, 3, 0)
+    idx[lo:hi] = -1
+    lo, hi = wave_span(B, 3, 1)
+    tile = rng.randint(0, size, TILE).astype(np.int64)
+    tile[0] = live[0]
+    tile[1], tile[3], tile[4], tile[5], tile[6], tile[7] = -1, size, cap - 1, 2 ** 31 - 1, tile[0], dead[0]
+    idx[lo:hi] = tile
+    mid = groups // 2
+    share = 0.5 if tpw <= 4 else 0.125
+    for W in (WAVES * mid, WAVES * mid + 1):
+        lo, hi = wave_span(B, W, 0, tpw - 1)
+        idx[lo:hi] = np.where(rng.rand(hi - lo) < share, rng.randint(0, size, hi - lo), -1)
+    return idx, dict(full=full, spread=1, late=3, mid=mid)
+
+
+def check_sparse(B, idx, ring, cap, plan):
+    """what sparse_indices() promises, asserted from launch_shape(B) and the vector alone -> effective(idx)"""
+    tiles, tpw, groups = launch_shape(B)
+    size = int(ring["size"])
+    eff = effective(idx, ring)
+    live = eff >= 0
+    assert tpw >= 2, "B = %d no longer gives a wavefront a second tile" % B
+    assert idx.shape == (B,) and int((idx != -1).sum()) <= VALID_MAX
+    # a wavefront with every tile fully valid in the last group, and in group 0 where the budget allows both
+    assert plan["full"] and plan["full"][-1] // WAVES == groups - 1
+    assert 4 * tpw * TILE >= VALID_MAX or plan["full"][0] // WAVES == 0
+    for W in plan["full"]:
+        lo, hi = wave_span(B, W, 0, tpw - 1)
+        assert hi > lo and live[lo:hi].all(), W
+    # valid samples at tiles 0, 1 and tiles_per_wave - 1 of one wavefront
+    for it in (0, 1, tpw - 1):
+        lo, hi = wave_span(B, plan["spread"], it)
+        assert 0 < live[lo:hi].sum() < TILE, it
+    # the last tile, ragged unless B is a multiple of the tile
+    lo = TILE * (tiles - 1)
+    assert live[lo:B].any() and (B - lo < TILE) == (B % TILE != 0)
+    # a wavefront whose first tile is empty and whose second is not; the second is the mixed tile
+    lo, hi = wave_span(B, plan["late"], 0)
+    assert hi - lo == TILE and not live[lo:hi].any()
+    lo, hi = wave_span(B, plan["late"], 1)
+    tile, tile_eff = idx[lo:hi], eff[lo:hi]
+    assert hi - lo == TILE and live[lo:hi].any()
+    assert {-1, size, cap - 1, 2 ** 31 - 1} <= set(tile.tolist())
+    assert ((tile >= 0) & (tile < size) & (tile_eff < 0)).any()                       # a slot with ok == 0
+    assert len(set(tile_eff[tile_eff >= 0].tolist())) < int((tile_eff >= 0).sum())    # a duplicate
+    # the middle group: partly filled tiles, first and later ones, in both wavefronts
+    for W in (WAVES * plan["mid"], WAVES * plan["mid"] + 1):
+        touched = [bool(live[slice(*wave_span(B, W, it))].any()) for it in range(tpw)]
+        assert sum(touched) > tpw // 2 and any(touched[1:]), W
+        lo, hi = wave_span(B, W, 0, tpw - 1)
+        assert not live[lo:hi].all()
+    with_valid = np.unique((np.nonzero(live)[0] // TILE) // (WAVES * tpw))
+    assert with_valid.size >= 3 and {0, 1, plan["mid"], groups - 1} <= set(with_valid.tolist())
+    return eff
 
 
 def float_ring(cap, size, seed, bad_ok=0.02):
