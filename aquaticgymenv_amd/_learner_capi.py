@@ -12,6 +12,8 @@ PARAMS = 4739                     # k0 [5][64], b0 [64], k1 [64][64], b1 [64], k
 MAX_BATCH = 1 << 20
 STREAM = 6                        # Philox stream of the minibatch draws
 STRATEGIES = {"double_ref": 0, "double": 1, "fixed": 2, "standard": 3}
+LOSS_REFERENCE = 16               # AQUALRN_LOSS_REFERENCE, OR-ed into the strategy argument
+LOSSES = {"mse": 0, "reference": LOSS_REFERENCE}
 
 # every symbol include/aqua_learner.h declares (tests/test_learner_cpu.py checks the library exports them all)
 SYMBOLS = ("aqualrn_version", "aqualrn_last_error", "aqualrn_workspace_bytes", "aqualrn_update_f32")

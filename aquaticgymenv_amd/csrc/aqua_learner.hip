@@ -1,5 +1,6 @@
 // aqua_learner.hip -- libaqua_learner.so (include/aqua_learner.h): one DQN update of the 5 -> 64 -> 64 -> 3 Q-network for a
-// minibatch of the device experience ring on gfx950 -- TD target, gradient (main/impl/dqn.py:238-292), Adam as Keras 2.3
+// minibatch of the device experience ring on gfx950 -- TD target (main/impl/dqn.py:262-292), gradient of the mean squared TD
+// error or, with AQUALRN_LOSS_REFERENCE, of the broadcast loss that dqn.py:243-247 executes, Adam as Keras 2.3
 // applies it (dqn.py:313), soft target update (dqn.py:294-299) and the re-pack into the acting network's blob -- in two
 // launches.  Its own translation unit and library: libaqua_hip.so, libaqua_policy.so and their kernels are not touched.
 //
@@ -55,8 +56,11 @@ constexpr int ATTEMPTS = 4;
 // across the tile.  A lane's slot: column (+ 6, 3 or 1 on the upper lane half) behind the base of its kind.
 constexpr int SLOT_K0 = 0, SLOT_K2 = 2 * (IN + 1), SLOT_B1 = SLOT_K2 + 2 * ACT, SMALL_SLOTS = SLOT_B1 + 2;
 
-// workspace: a 16-byte header (uint64 t + 1) and, per workgroup, PARAMS partial sums, the number of valid samples (int32
-// bits) and the partial loss (the squares of the unrounded delta summed in double: one number, so its own rounding should not show)
+// workspace: a 16-byte header (uint64 t + 1) and, per workgroup, PARAMS partial sums, the number n of squares in the loss
+// (int32 bits: the valid samples, times 3 with AQUALRN_LOSS_REFERENCE, so that the apply kernel's 2 / n and sum / n are
+// 2 / (3 B_eff) and sum / (3 B_eff) and that kernel does not know the form) and the partial loss (the squares of the
+// unrounded delta -- of the three differences Q_a - T_j with the flag -- summed in double: one number, so its own rounding
+// should not show)
 constexpr int WS_HEADER = 16;
 constexpr int WS_COUNT = PARAMS, WS_LOSS = PARAMS + 1, WS_USED = PARAMS + 3, WS_STRIDE = 4744;   // the loss: a double in two slots
 static_assert(WS_USED <= WS_STRIDE && WS_STRIDE % 4 == 0 && WS_LOSS % 2 == 0, "a partial is 16-byte aligned, its loss 8-byte");
@@ -81,6 +85,7 @@ struct GradArgs {
     uint64_t seed;
     float gamma;
     int tiles_per_wave;
+    int loss_ref;                            // AQUALRN_LOSS_REFERENCE: the broadcast of dqn.py:243-247 in place of the squared TD error
     uint64_t* ws_t;
     float* ws;
     int32_t* idx_out;
@@ -276,9 +281,18 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
         if constexpr (STRAT == AQUALRN_DOUBLE_REF) f = pick3(qb, argmax3(q));
 
         const double y = done ? static_cast<double>(rew) : fma(static_cast<double>(a.gamma), f, static_cast<double>(rew));
-        const double delta64 = valid ? pick3(q, act) - y : 0.0;
+        const double qa = pick3(q, act);
+        double delta64 = valid ? qa - y : 0.0;
+        double sq = delta64 * delta64;
+        if (a.loss_ref != 0) {
+            // T_j = y for the action taken, Q(s)[j] (a constant) for the other two: d/dQ_a of sum_j (Q_a - T_j)^2 over 2
+            const double qo1 = act == 0 ? q[1] : q[0], qo2 = act == 2 ? q[1] : q[2];
+            const double e1 = qa - qo1, e2 = qa - qo2;
+            delta64 = valid ? 3.0 * qa - y - qo1 - qo2 : 0.0;
+            sq = valid ? sq + e1 * e1 + e2 * e2 : 0.0;
+        }
         const float delta = static_cast<float>(delta64);     // the one rounding between h2 and the backward pass
-        loss += delta64 * delta64;
+        loss += sq;
         count += valid ? 1 : 0;
 #pragma unroll
         for (int c = 0; c < ACT; ++c) db2[c] += act == c ? delta : 0.0f;
@@ -407,7 +421,8 @@ __global__ __launch_bounds__(BLOCK) void lrn_grad_kernel(const GradArgs a)
     if (h == 0) {
 #pragma unroll
         for (int c = 0; c < ACT; ++c) sm[wave][c][col] = db2[c];
-        sm[wave][3][col] = __int_as_float(count);
+        // what the apply kernel divides by: the squares the mean runs over, 3 per valid sample with AQUALRN_LOSS_REFERENCE
+        sm[wave][3][col] = __int_as_float(a.loss_ref != 0 ? ACT * count : count);
         sl[wave][col] = loss;
     }
     float* const red = stage;
@@ -589,6 +604,8 @@ int aqualrn_update_f32(float* theta, float* theta_target, float* m, float* v, ui
     if (B < 0 || B > AQUALRN_MAX_BATCH) return fail(AQUALRN_E_INVALID, "B=%lld: must be in [0, %d]", (long long)B, AQUALRN_MAX_BATCH);
     if (ld < 0 || size < 0 || size > ld || ld > INT32_MAX)
         return fail(AQUALRN_E_INVALID, "bad ring sizes: size=%lld ld=%lld", (long long)size, (long long)ld);
+    const int loss_ref = (strategy & AQUALRN_LOSS_REFERENCE) != 0 ? 1 : 0;
+    if (strategy >= 0) strategy &= ~AQUALRN_LOSS_REFERENCE;          // what is left: the bootstrap strategy, no other bit
     if (strategy < AQUALRN_DOUBLE_REF || strategy > AQUALRN_STANDARD) return fail(AQUALRN_E_INVALID, "strategy=%d: unknown", strategy);
     if (!is_number(gamma) || !(gamma >= 0.0 && gamma <= 1.0)) return fail(AQUALRN_E_INVALID, "gamma=%g: must be in [0, 1]", gamma);
     if (!is_number(tau) || !(tau >= 0.0 && tau <= 1.0)) return fail(AQUALRN_E_INVALID, "tau=%g: must be in [0, 1]", tau);
@@ -623,6 +640,7 @@ int aqualrn_update_f32(float* theta, float* theta_target, float* m, float* v, ui
     g.ld = ld; g.size = size; g.B = B; g.idx = idx; g.seed = seed;
     g.gamma = static_cast<float>(gamma);
     g.tiles_per_wave = sh.tiles_per_wave;
+    g.loss_ref = loss_ref;
     g.ws_t = static_cast<uint64_t*>(workspace);
     g.ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + WS_HEADER);
     g.idx_out = idx_out;

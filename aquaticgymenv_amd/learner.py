@@ -1,7 +1,15 @@
-"""DQNLearner: the reference's training step (main/impl/dqn.py:175-176 with its defaults: the "double" target as
-dqn.py:262-272 executes it, the custom-gradient mean squared error of dqn.py:238-249, Keras 2.3's Adam of dqn.py:313, the
-soft target update of dqn.py:294-299) for a minibatch of a ReplayRing, on the device by libaqua_learner.so
-(include/aqua_learner.h).
+"""DQNLearner: the reference's training step (main/impl/dqn.py:175-176: the "double" target as dqn.py:262-272 executes
+it, a squared-error loss, Keras 2.3's Adam of dqn.py:313, the soft target update of dqn.py:294-299) for a minibatch of a
+ReplayRing, on the device by libaqua_learner.so (include/aqua_learner.h).
+
+The loss has three forms (T_bj = y_b for j = a_b and Q(s_b)[j] otherwise, held constant):
+  loss="reference"  what the reference's default "custom_grad" step executes: dqn.py:244 keeps the prediction [B,1],
+                    dqn.py:246 subtracts the whole [B,3] target array, the difference broadcasts and dqn.py:247 averages
+                    3 B elements: L = 1/(3B) sum_b sum_j (Q_a - T_bj)^2, gradient 2/(3B) (3 Q_a - y - sum_{j != a} Q_j).
+  (not offered)     its "standard" step, train_on_batch with Keras "mse" (dqn.py:236, 313): 1/(3B) sum_b (Q_a - y)^2, the
+                    textbook direction with a factor 1/3.
+  loss="mse"        the default here: the textbook 1/B sum_b (Q_a - y)^2, gradient 2/B_eff (Q_a - y) -- neither of the
+                    reference's paths exactly; it differs from "reference" in direction, not only in scale.
 
 Two launches per update, no allocation, no synchronisation, no host read: update() works unchanged inside
 torch.cuda.graph.  The new weights are scattered into the acting QNetwork's device blob, so env.step(policy=qnet) and a
@@ -18,13 +26,16 @@ from . import _learner_capi
 class DQNLearner(object):
     BETA1, BETA2, EPS = 0.9, 0.999, 1e-7          # tf.keras.optimizers.Adam's defaults (dqn.py:313)
 
-    def __init__(self, qnet, gamma=0.98, tau=0.005, lr=1e-3, strategy="double_ref", seed=0):
+    def __init__(self, qnet, gamma=0.98, tau=0.005, lr=1e-3, strategy="double_ref", seed=0, loss="mse"):
         """qnet: the acting QNetwork; theta and theta_target start from qnet.layers.  gamma, tau, lr: default_hyperparam's.
-        strategy: "double_ref" (what dqn.py:267-268 executes), "double" (what its comment says), "fixed", "standard"."""
+        strategy: "double_ref" (what dqn.py:267-268 executes), "double" (what its comment says), "fixed", "standard".
+        loss: "mse" (the mean squared TD error) or "reference" (the broadcast dqn.py:243-247 executes), see above."""
         if not getattr(qnet, "_aquapol_network", False):
             raise ValueError("expected a QNetwork")
         if strategy not in _learner_capi.STRATEGIES:
             raise ValueError("strategy %r: one of %s" % (strategy, sorted(_learner_capi.STRATEGIES)))
+        if loss not in _learner_capi.LOSSES:
+            raise ValueError("loss %r: one of %s" % (loss, sorted(_learner_capi.LOSSES)))
         torch = qnet.torch
         self.torch = torch
         self.qnet = qnet
@@ -32,6 +43,7 @@ class DQNLearner(object):
         self.gamma, self.tau, self.lr = float(gamma), float(tau), float(lr)
         self.beta1, self.beta2, self.eps = self.BETA1, self.BETA2, self.EPS
         self.strategy = strategy
+        self.loss_form = loss
         self.seed = int(seed) & ((1 << 64) - 1)
         dev = self.device
         n = _learner_capi.PARAMS
@@ -94,7 +106,7 @@ class DQNLearner(object):
                 ring.s.data_ptr(), ring.a.data_ptr(), ring.r.data_ptr(), ring.s2.data_ptr(), ring.d.data_ptr(),
                 ring.ok.data_ptr(), cap, int(ring.size),
                 None if idx is None else idx.data_ptr(), B, self.seed,
-                _learner_capi.STRATEGIES[self.strategy], self.gamma, self.tau, self.lr, self.beta1, self.beta2, self.eps,
+                _learner_capi.STRATEGIES[self.strategy] | _learner_capi.LOSSES[self.loss_form], self.gamma, self.tau, self.lr, self.beta1, self.beta2, self.eps,
                 self.qnet.blob.data_ptr(), self.target_blob.data_ptr(), self.perm.data_ptr(), self.qnet.blob.numel() // 4,
                 self._workspace.data_ptr(), need,
                 None if idx_out is None else idx_out.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), self._stream())
@@ -114,7 +126,7 @@ class DQNLearner(object):
     def state_dict(self):
         out = {name: getattr(self, name).detach().cpu().clone() for name in ("theta", "theta_target", "m", "v", "t")}
         out["hyper"] = {"gamma": self.gamma, "tau": self.tau, "lr": self.lr, "beta1": self.beta1, "beta2": self.beta2,
-                        "eps": self.eps, "strategy": self.strategy, "seed": self.seed}
+                        "eps": self.eps, "strategy": self.strategy, "seed": self.seed, "loss": self.loss_form}
         return out
 
     def load_state_dict(self, state):
@@ -131,9 +143,13 @@ class DQNLearner(object):
         h = state.get("hyper", {})
         if h.get("strategy", self.strategy) not in _learner_capi.STRATEGIES:
             raise ValueError("strategy %r" % (h["strategy"],))
+        if h.get("loss", "mse") not in _learner_capi.LOSSES:
+            raise ValueError("loss %r" % (h["loss"],))
         for key in ("gamma", "tau", "lr", "beta1", "beta2", "eps", "strategy", "seed"):
             if key in h:
                 setattr(self, key, h[key])
+        if "hyper" in state:
+            self.loss_form = h.get("loss", "mse")            # absent in checkpoints written before the option existed
         self.qnet.load(_learner_capi.unflatten(np.asarray(state["theta"])))
         self.target_blob.copy_(torch.from_numpy(_policy_capi.pack_weights(_learner_capi.unflatten(np.asarray(state["theta_target"])))))
         return self

@@ -39,6 +39,8 @@ ap.add_argument("--buffer", type=int, default=1 << 20, help="ring capacity in tr
 ap.add_argument("--obstacles", action="store_true")
 ap.add_argument("--epsilon-decay", type=float, default=10000, help="a factor, or the number of episodes to reach the final epsilon")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--loss", choices=("mse", "reference"), default="mse",
+                help="mse: the mean squared TD error; reference: the broadcast loss main/impl/dqn.py:243-247 executes")
 ap.add_argument("--eager", action="store_true", help="issue every launch of the iteration from Python (ReplayRing) instead of replaying one graph")
 args = ap.parse_args()
 
@@ -51,7 +53,7 @@ for fan_in, fan_out in ((5, 64), (64, 64), (64, 3)):          # Keras' default: 
     lim = np.sqrt(6.0 / (fan_in + fan_out))
     layers.append((rng.uniform(-lim, lim, (fan_in, fan_out)).astype(np.float32), np.zeros(fan_out, dtype=np.float32)))
 qnet = QNetwork(layers, "cuda")
-learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref", seed=args.seed)
+learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref", seed=args.seed, loss=args.loss)
 
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()

@@ -3,9 +3,21 @@
  * of the acting network's weights) for a minibatch of a device experience ring, on MI355X (gfx950), next to the Q-network
  * of aqua_policy.h and the batched environment of aqua_hip.h.
  *
- * Reference being replaced: main/impl/dqn.py:175-176 with its defaults -- IMPROVE_STRATEGY = _improve_network_gradient
- * (dqn.py:238-249), LOSS_STRATEGY = _improve_strategy_double (dqn.py:262-272), the Adam of dqn.py:313 as Keras 2.3 applies
- * it, and _improve_target_network (dqn.py:294-299).
+ * Reference being replaced: main/impl/dqn.py:175-176 with its defaults -- LOSS_STRATEGY = _improve_strategy_double
+ * (dqn.py:262-272), the Adam of dqn.py:313 as Keras 2.3 applies it, and _improve_target_network (dqn.py:294-299).
+ *
+ * The loss has three forms (T_bj = y_b for j = a_b, Q(s_b)[j] otherwise, T and y held constant):
+ *   "custom_grad", the reference's default IMPROVE_STRATEGY = _improve_network_gradient (dqn.py:238-249), AS IT EXECUTES:
+ *       the [B,1] prediction (keepdims, dqn.py:244) is subtracted from the whole [B,3] target array (dqn.py:246), the
+ *       difference broadcasts and reduce_mean runs over 3 B elements:
+ *           L_ref = 1/(3 B) sum_b sum_j (Q(s_b)[a_b] - T_bj)^2,   dL_ref/dQ(s_b)[a_b] = 2/(3 B) (3 Q_a - y - sum_{j != a} Q_j)
+ *       This is AQUALRN_LOSS_REFERENCE.  Its gradient differs from the next two in direction, not only in scale.
+ *   "standard", IMPROVE_STRATEGY = _improve_network (dqn.py:230-236): train_on_batch with Keras "mse" (dqn.py:313) on [B,3]
+ *       outputs against T, 1/(3 B) sum_b (Q_a - y)^2: the textbook direction with a factor 1/3.  Not offered.
+ *   the library's default, the textbook mean squared TD error 1/B sum_b (Q_a - y)^2: gradient 2/B_eff (Q_a - y).  It is
+ *       neither of the reference's two paths exactly.
+ * tests/_learner_autograd.py differentiates the first and the third with autograd; tests/test_learner_model_cpu.py and
+ * tests/test_learner_forms_gpu.py hold the model and the kernels to it.
  *
  * Conventions are those of aqua_policy.h:
  *  - plain pointers and sizes only (streams are void*); every DEVICE buffer is owned by the caller and borrowed until
@@ -24,7 +36,9 @@
  * Numerics: float32 forward and backward, no reduced-precision operand anywhere; the last layer, y and delta_b =
  * Q(s_b)[a_b] - y_b are evaluated in double from the float32 hidden activations and delta_b is rounded once (it is a
  * difference of long sums that multiplies every gradient element; the loss is the mean of the unrounded delta_b^2).
- * Every gradient element is the float32 sum S of its per-sample terms, multiplied ONCE by float32(2.0 / B_eff).  No
+ * Every gradient element is the float32 sum S of its per-sample terms, multiplied ONCE by float32(2.0 / B_eff).  With
+ * AQUALRN_LOSS_REFERENCE delta_b = 3 Q_a - y - sum_{j != a} Q_j from the same three double Q-values, rounded once, the
+ * factor is float32(2.0 / (3 B_eff)) and the loss the double sum of the 3 B_eff squares over 3 B_eff.  No
  * floating-point atomics: which samples are added into which partial sum, and the order in which the partial sums are
  * added, are functions of B alone (not of the grid, not of the device), so the same inputs give the same bits run to run,
  * eager or replayed from a graph.  Adam and the soft update are evaluated in double from the float32 state and rounded
@@ -59,6 +73,8 @@ extern "C" {
 #define AQUALRN_DOUBLE      1      /* Q_target(s')[argmax Q_online(s')]  what its comment says */
 #define AQUALRN_FIXED       2      /* max Q_target(s')                   dqn.py:274-282 */
 #define AQUALRN_STANDARD    3      /* max Q_online(s')                   dqn.py:284-292 */
+/* a flag OR-ed into `strategy`: the loss as dqn.py:243-247 executes it (see above); without it the mean squared TD error */
+#define AQUALRN_LOSS_REFERENCE 16
 
 int aqualrn_version(void);                 /* AQUALRN_ABI_VERSION */
 const char* aqualrn_last_error(void);
@@ -81,9 +97,11 @@ size_t aqualrn_workspace_bytes(int64_t B);
  *                               the first attempt a = 0..3 whose ok[idx] != 0 wins.  In both forms a sample is VALID iff
  *                               0 <= idx < size and ok[idx] != 0; an index outside [0, size) is never dereferenced and an
  *                               invalid sample contributes nothing.  B_eff = number of valid samples.
- *   strategy                  : AQUALRN_DOUBLE_REF .. AQUALRN_STANDARD; arg-max takes the lowest index on a tie.
+ *   strategy                  : AQUALRN_DOUBLE_REF .. AQUALRN_STANDARD, optionally | AQUALRN_LOSS_REFERENCE; any other bit is
+ *                               AQUALRN_E_INVALID.  arg-max takes the lowest index on a tie.
  *   gamma, tau in [0, 1]; lr >= 0; beta1, beta2 in [0, 1); eps > 0; all finite (otherwise AQUALRN_E_INVALID).
  *       L      = (1 / B_eff) sum_b (Q_online(s_b)[a_b] - y_b)^2, y constant
+ *                (AQUALRN_LOSS_REFERENCE: 1 / (3 B_eff) sum_b sum_j (Q_online(s_b)[a_b] - T_bj)^2, T constant)
  *       t     <- t + 1;  lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in double from the device counter, rounded once
  *       m     <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;  theta <- theta - lr_t m / (sqrt(v) + eps)
  *       theta_target <- tau theta + (1 - tau) theta_target       (with the NEW theta; tau = 1 copies, tau = 0 leaves it)

@@ -11,6 +11,7 @@ from tests import _placement as P
 PARAMS = 4739
 SHAPES = ((5, 64), (64, 64), (64, 3))
 STRATEGIES = ("double_ref", "double", "fixed", "standard")
+FORMS = ("mse", "reference")     # the loss: the textbook mean squared error / the broadcast main/impl/dqn.py:243-247 executes
 STREAM = 6
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-7
 TILE, WAVES, GMAX = 32, 2, 512     # samples per tile, wavefronts per workgroup, workgroups at most (csrc/aqua_learner.hip)
@@ -93,9 +94,14 @@ def bootstrap(theta, theta_t, x, x2, strategy):
     return forward(theta, x2)[2].max(axis=1), None
 
 
-def gradient(theta32, theta_t32, ring, eff, gamma, strategy, dtype):
+def gradient(theta32, theta_t32, ring, eff, gamma, strategy, dtype, form="mse"):
     """loss and gradient of the valid samples `eff` (effective()'s output), every operation in `dtype`:
-    -> dict(g [PARAMS], S (the unscaled sums), loss, n, delta, deciding)"""
+    -> dict(g [PARAMS], S (the unscaled sums), loss, n, delta, deciding)
+    form "mse": L = 1/n sum_b (Q(s_b)[a_b] - y_b)^2, the textbook loss.  form "reference": what main/impl/dqn.py:243-247
+    executes, the [B,1] prediction broadcast against the [B,3] targets T (T_bj = y_b for j = a_b, Q(s_b)[j] otherwise, held
+    constant): L = 1/(3n) sum_b sum_j (Q(s_b)[a_b] - T_bj)^2, so dL/dQ(s_b)[a_b] = 2/(3n) (3 Q_a - y - sum_{j != a} Q_j).
+    tests/_learner_autograd.py differentiates both without this derivation."""
+    assert form in FORMS, form
     theta, theta_t = theta32.astype(dtype), theta_t32.astype(dtype)
     x, a, r, x2, done = batch_of(ring, eff, dtype)
     n = x.shape[0]
@@ -106,22 +112,32 @@ def gradient(theta32, theta_t32, ring, eff, gamma, strategy, dtype):
     y = r + np.where(done, dtype(0), dtype(gamma) * f).astype(dtype)
     h1, h2, q = forward(theta, x)
     (k0, b0), (k1, b1), (k2, b2) = unflatten(theta)
-    delta = (q[np.arange(n), a] - y).astype(dtype)
+    qa = q[np.arange(n), a]
+    if form == "reference":
+        taken = np.arange(3)[None, :] == a[:, None]
+        rest = np.where(taken, dtype(0), q).sum(axis=1, dtype=dtype)
+        delta = (dtype(3) * qa - y - rest).astype(dtype)
+        sq = (qa[:, None] - np.where(taken, y[:, None], q)) ** 2
+        scale, mean = dtype(2.0 / (3 * n)), dtype(1.0 / (3 * n))
+    else:
+        delta = (qa - y).astype(dtype)
+        sq = delta * delta
+        scale, mean = dtype(2.0 / n), dtype(1.0 / n)
     dq = np.zeros((n, 3), dtype=dtype)
     dq[np.arange(n), a] = delta
     dh2 = (dq @ k2.T) * (h2 > 0)
     dh1 = (dh2 @ k1.T) * (h1 > 0)
     S = flatten([(x.T @ dh1, dh1.sum(axis=0)), (np.maximum(h1, 0).T @ dh2, dh2.sum(axis=0)), (np.maximum(h2, 0).T @ dq, dq.sum(axis=0))])
-    assert S.dtype == dtype and delta.dtype == dtype
-    g = S * dtype(2.0 / n)
-    loss = (delta * delta).sum(dtype=dtype) * dtype(1.0 / n)
+    assert S.dtype == dtype and delta.dtype == dtype and sq.dtype == dtype
+    g = S * scale
+    loss = sq.sum(dtype=dtype) * mean
     return dict(g=g, S=S, loss=loss, n=n, delta=delta, deciding=deciding, done=done)
 
 
-def abs_sums(theta_i, theta_t_i, ring, eff, strategy):
+def abs_sums(theta_i, theta_t_i, ring, eff, strategy, form="mse"):
     """Integer networks and data: the largest sum of |terms| over every intermediate and every gradient element, in int64
     (an upper bound of every partial sum in any order), and the exact unscaled gradient sums S."""
-    out = gradient(theta_i.astype(np.int64).astype(np.float64), theta_t_i.astype(np.float64), ring, eff, 1.0, strategy, np.float64)
+    out = gradient(theta_i.astype(np.int64).astype(np.float64), theta_t_i.astype(np.float64), ring, eff, 1.0, strategy, np.float64, form)
     x, a, r, x2, done = batch_of(ring, eff, np.int64)
     n = x.shape[0]
     worst = 0
@@ -135,6 +151,8 @@ def abs_sums(theta_i, theta_t_i, ring, eff, strategy):
     (k0, b0), (k1, b1), (k2, b2) = unflatten(np.abs(theta_i.astype(np.int64)))
     h1, h2, q = forward(np.abs(theta_i.astype(np.int64)), np.abs(x))
     delta = q.max(axis=1) + np.abs(r) + qmax.max(axis=1)                 # |Q(s)[a]| + |r| + |f|, each bounded by its sum of |terms|
+    if form == "reference":
+        delta = delta + 2 * q.max(axis=1) + q.sum(axis=1)                # 3 |Q_a| + |r| + |f| + sum_j |Q_j|, bounded the same way
     dq = np.repeat(delta[:, None], 3, axis=1)
     dh2 = dq @ k2.T
     dh1 = dh2 @ k1.T

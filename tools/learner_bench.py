@@ -53,7 +53,7 @@ for fi, fo in ((5, 64), (64, 64), (64, 3)):
 
 
 def torch_side():
-    """dqn.py:262-272 + 238-249 + 294-299 with torch: -> update(idx)"""
+    """dqn.py:262-272, the mean squared TD error (DQNLearner's loss="mse") and dqn.py:294-299 with torch: -> update(idx)"""
     online = [torch.tensor(z, device=DEV, requires_grad=True) for kb in layers for z in kb]
     target = [p.detach().clone() for p in online]
     opt = torch.optim.Adam(online, lr=LR, betas=(0.9, 0.999), eps=1e-7)
