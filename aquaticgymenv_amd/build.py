@@ -48,11 +48,16 @@ EXTRA_LIBRARIES = {
 ADDON_LIBRARIES = {
     "replay": _library("replay", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
 }
+# Libraries behind those (the three tables above and what every_library() returns are pinned as well).
+# bank: a bank of Q-networks acting on one batch in one launch (include/aqua_bank.h).
+BANK_LIBRARIES = {
+    "bank": _library("bank", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
 
 
 def library(name):
-    """the table entry of library `name`, from LIBRARIES, EXTRA_LIBRARIES or ADDON_LIBRARIES"""
-    for table in (LIBRARIES, EXTRA_LIBRARIES):
+    """the table entry of library `name`, from LIBRARIES, EXTRA_LIBRARIES, ADDON_LIBRARIES or BANK_LIBRARIES"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -64,8 +69,13 @@ def all_libraries():
 
 
 def every_library():
-    """every library's name, the add-ons included, in build order (what build() and `python -m` compile)"""
+    """every library's name up to the add-ons, in build order"""
     return all_libraries() + list(ADDON_LIBRARIES)
+
+
+def each_library():
+    """every library's name, those of BANK_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return every_library() + list(BANK_LIBRARIES)
 
 
 def hipcc_path():
@@ -114,6 +124,8 @@ RENDER_SRC, RENDER_DEPS, RENDER_LIB, RENDER_FLAGS = (EXTRA_LIBRARIES["render"][k
 build_render, render_needs_build = functools.partial(build_library, "render"), functools.partial(needs_build, "render")
 REPLAY_SRC, REPLAY_DEPS, REPLAY_LIB, REPLAY_FLAGS = (ADDON_LIBRARIES["replay"][k] for k in ("src", "deps", "lib", "flags"))
 build_replay, replay_needs_build = functools.partial(build_library, "replay"), functools.partial(needs_build, "replay")
+BANK_SRC, BANK_DEPS, BANK_LIB, BANK_FLAGS = (BANK_LIBRARIES["bank"][k] for k in ("src", "deps", "lib", "flags"))
+build_bank, bank_needs_build = functools.partial(build_library, "bank"), functools.partial(needs_build, "bank")
 
 
 def build_variant(name, flags, verbose=False):
@@ -163,5 +175,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in every_library():
+    for name in each_library():
         print(build_library(name, force="--force" in sys.argv, verbose=True))

@@ -1,6 +1,7 @@
 """The device assembly of one of the project's HIP libraries and its kernels, as the compiler reports them (no GPU
 needed).  tools/make_policy_isa_budget.py, tools/learner_isa.py and tools/episodes_isa.py print it; tests/test_qpolicy_cpu.py,
-tests/test_learner_cpu.py, tests/test_episodes_cpu.py and tests/test_replay_cpu.py gate the same listing.
+tests/test_learner_cpu.py, tests/test_episodes_cpu.py, tests/test_replay_cpu.py and tests/test_qbank_cpu.py gate the same
+listing.
 """
 import os
 import re
@@ -14,7 +15,7 @@ if ROOT not in sys.path:
 
 
 def listing(name):
-    """-> the device assembly of library `name` of aquaticgymenv_amd.build (LIBRARIES, EXTRA_LIBRARIES or ADDON_LIBRARIES) as text, compiled with the library's flags"""
+    """-> the device assembly of library `name` of aquaticgymenv_amd.build (any of its tables) as text, compiled with the library's flags"""
     from aquaticgymenv_amd import build
     entry = build.library(name)
     flags = [f for f in entry["flags"] if f not in ("-shared", "-fPIC")]
