@@ -210,3 +210,88 @@ def test_adam64_against_torch_adam_without_eps():
         # rounding is 2^-53 |theta| = 4e-17 here
         assert np.max(np.abs(p.detach().numpy() - th64)) <= 1e-12 * lr
         theta, m, v = f32(th64), f32(m64), f32(v64)
+
+
+# ------------------------------------------------------------------------------------------------ where Adam's eps goes
+ADAM_STEPS = (1, 2, 1000)
+ADAM_ROOTS = (0.0, 1e-9, 1e-7, 1e-5, 1e-1)        # sqrt(v) after the step: 0, far below eps = 1e-7, at it, above, far above
+
+
+def _adam_case(t):
+    """float32 state whose sqrt(v') after step t is ADAM_ROOTS x eight m of both signs x a gradient that is zero (v' = beta2 v
+    exactly on the grid) or not -> (theta, m, v, g) float32 [80]"""
+    rng = np.random.RandomState(t)
+    roots, ms, gs = np.meshgrid(np.array(ADAM_ROOTS), np.array([1e-9, -1e-6, 1e-3, -1e-1, -1e-9, 1e-6, -1e-3, 1e-1]), np.array([0.0, 1.0]), indexing="ij")
+    v = (roots.reshape(-1) ** 2 / L.BETA2).astype(np.float32)
+    g = (gs.reshape(-1) * rng.uniform(-1, 1, v.size) * roots.reshape(-1)).astype(np.float32)      # |g| <= sqrt(v): the root stays of its order
+    return rng.uniform(-1, 1, v.size).astype(np.float32), ms.reshape(-1).astype(np.float32), v, g
+
+
+def _adam_compare(model, t, eps=L.EPS, lr=1e-3):
+    """`model`: L.adam64 or a mutant of it, one step to t, against torch.optim.Adam in float64 with eps / sqrt(1 - beta2^t)"""
+    import torch
+    theta, m, v, g = _adam_case(t)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        th64, m64, v64, t1 = model(theta, theta, m, v, t - 1, g, lr, 0.005, eps=eps)
+    assert t1 == t
+    p = torch.nn.Parameter(torch.tensor(theta.astype(np.float64)))
+    opt = torch.optim.Adam([p], lr=lr, betas=(L.BETA1, L.BETA2), eps=eps / np.sqrt(1.0 - L.BETA2 ** t))
+    p.grad = torch.zeros_like(p)
+    opt.step()                                             # creates the state; everything it touched is overwritten below
+    state = opt.state[p]
+    with torch.no_grad():
+        p.copy_(torch.tensor(theta.astype(np.float64)))
+        state["exp_avg"].copy_(torch.tensor(m.astype(np.float64)))
+        state["exp_avg_sq"].copy_(torch.tensor(v.astype(np.float64)))
+        if torch.is_tensor(state["step"]):
+            state["step"].fill_(t - 1)
+        else:
+            state["step"] = t - 1
+    p.grad = torch.tensor(g.astype(np.float64))
+    opt.step()
+    assert int(state["step"]) == t
+    got, theta64 = p.detach().numpy(), theta.astype(np.float64)
+    step_t = got - theta64
+    assert np.isfinite(step_t).all() and (step_t != 0).all()
+    root = np.sqrt(state["exp_avg_sq"].numpy())
+    assert (root == 0).sum() >= 8 and ((root > 0) & (root < 0.1 * eps)).sum() >= 8 and (root > 100 * eps).sum() >= 16
+    # float64 rounding: a dozen operations on the step, one on theta -- 1e-12 of the step is a condition, as BOUND is
+    err = np.abs(th64 - got)
+    bar = 1e-12 * np.abs(step_t) + 2.0 ** -52 * np.abs(theta64)
+    assert bool((err <= bar).all()), "t = %d: worst %.3e of the step" % (t, float(np.nanmax(err / np.abs(step_t))))
+    assert np.max(np.abs(state["exp_avg"].numpy() - m64)) <= 1e-15 and np.max(np.abs(state["exp_avg_sq"].numpy() - v64) / np.maximum(v64, 1e-300)) <= 1e-12
+    return float(np.max(err / np.abs(step_t)))
+
+
+@pytest.mark.parametrize("t", ADAM_STEPS)
+def test_adam64_puts_eps_where_keras_puts_it(t):
+    """Keras 2.3 (main/impl/dqn.py:313):  theta -= lr_t m / (sqrt(v) + e),  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t).
+    torch.optim.Adam:                    theta -= lr / (1 - b1^t)  m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+    Multiply torch's numerator and denominator by sqrt(1 - b2^t):
+                                         theta -= lr_t m / (sqrt(v) + eps sqrt(1 - b2^t)),
+    so one Keras step with epsilon e at step t IS one torch step with eps = e / sqrt(1 - b2^t): an implementation that
+    shares no code with L.adam64 and pins where eps goes -- added to the root, outside the bias correction -- and its
+    value, on parameters whose sqrt(v) runs from 0 through e to far above it, where e decides the step."""
+    print("t = %d: worst |theta_adam64 - theta_torch| = %.1e of the step" % (t, _adam_compare(L.adam64, t)))
+
+
+def _adam_mutant(old, new):
+    src = inspect.getsource(L.adam64)
+    assert src.count(old) == 1, old
+    scope = dict(vars(L))
+    exec(compile(src.replace(old, new), "<mutant of tests/_learner.py::adam64>", "exec"), scope)
+    return scope["adam64"]
+
+
+ADAM_MUTANTS = {
+    "eps dropped": ("(np.sqrt(v2) + eps)", "(np.sqrt(v2) + 0.0)"),
+    "eps inside the root": ("(np.sqrt(v2) + eps)", "np.sqrt(v2 + eps)"),
+    "eps 1e-8": ("(np.sqrt(v2) + eps)", "(np.sqrt(v2) + 1e-8)"),
+}
+
+
+@pytest.mark.parametrize("t", ADAM_STEPS)
+@pytest.mark.parametrize("name", sorted(ADAM_MUTANTS))
+def test_the_adam_comparison_rejects_a_misplaced_eps(name, t):
+    with pytest.raises(AssertionError):
+        _adam_compare(_adam_mutant(*ADAM_MUTANTS[name]), t)
