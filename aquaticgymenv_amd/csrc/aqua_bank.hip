@@ -1,20 +1,15 @@
 // aqua_bank.hip -- libaqua_bank.so (include/aqua_bank.h): a bank of the DQN's 5 -> 64 -> 64 -> 3 Q-networks
 // (main/impl/dqn.py:301-314) acting on one batch of worlds in one launch on gfx950; network p takes the p-th segment of
-// the batch.  Its own translation unit and library: libaqua_policy.so, whose kernel this one reproduces bit for bit per
+// the batch.  Its own translation unit and library: libaqua_policy.so, whose results this one reproduces bit for bit per
 // segment, is not touched by it and stays the packer of the weights.
 //
-// Layout: qpolicy_kernel's.  WORLDS sit on the column index of v_mfma_f32_32x32x2_f32 (one tile
-// = 32 worlds per wavefront), UNITS on its rows; a layer's accumulator tile is, register by register, the B operand of
-// the next layer; layer 3 runs on the VALU; the activations never leave the registers.  The A operands are per wavefront,
-// so a tile belongs to ONE network: the unit of work is the item (network p, tile j of p's segment), and every wavefront
-// takes a contiguous run of items, reloading its weights (70 VGPRs, and a 324-float LDS part of its own) only where
-// the network changes inside the run.
-//
-// Numerics: float32, every unit one fmaf chain from its bias (the MFMA is bit for bit a k-ordered fmaf chain); the three
-// outputs are two 32-term fmaf chains (one per lane half, the first starting at the bias) added once.
+// The network itself -- the blob's layout (one slot of the bank is one blob), the forward pass of a tile, the pick and
+// its stores -- is stated in aqua_qnet.hpp, once for this library and libaqua_policy.so.  Here:
+// the A operands are per wavefront, so a tile belongs to ONE network: the unit of work is the item (network p, tile j of
+// p's segment), and every wavefront takes a contiguous run of items, reloading its weights (70 VGPRs, and a 324-float
+// LDS part of its own) only where the network changes inside the run.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 
 #include "../../include/aqua_bank.h"
@@ -24,32 +19,12 @@
 
 namespace aqua_bank {
 
-using aqua::draw;
-using aqua::u_01;
 using namespace aqua::qnet;
 
 static_assert(STREAM_POLICY == AQUABANK_STREAM, "aqua_bank.h names the stream of the policy draws");
 static_assert(IN == AQUABANK_INPUTS && HID == AQUABANK_HIDDEN && ACT == AQUABANK_ACTIONS, "aqua_bank.h names the network's sizes");
-constexpr int K1_STEPS = 3;              // layer 1: K = 5 padded to 6 (the sixth weight and input are zero)
-constexpr int K2_STEPS = HID / 2;        // layer 2: 32 k-steps of 2 for each of the two row blocks
 constexpr int BLOCK = 256, WAVES = BLOCK / 64;
 constexpr int WAVES_PER_SIMD = 3;        // resident wavefronts per SIMD = blocks per CU (<= 170 registers each)
-
-// One slot of the bank, in floats: the blob of aquapol_pack_weights(), restated (aqua_policy.hip keeps its constants to
-// itself; tests/test_qbank_cpu.py pins these against the real packer through aquabank_unpack_weights()).  W1 / W2: the A
-// operands, one float per lane and (k-step, row block).  The rest is what the kernel keeps in LDS, in the order a lane
-// half reads it: biases of the hidden layers as the accumulators' initial values, the output layer's weights per action,
-// its bias.
-constexpr int OFF_W1 = 0;                                   // [K1_STEPS][2][64]
-constexpr int OFF_W2 = OFF_W1 + K1_STEPS * 2 * 64;          // [2][K2_STEPS][64]
-constexpr int OFF_LDS = OFF_W2 + 2 * K2_STEPS * 64;
-constexpr int LDS_B0 = 0;                                   // [2 halves][32]
-constexpr int LDS_B1 = LDS_B0 + 64;                         // [2 halves][32]
-constexpr int LDS_K2 = LDS_B1 + 64;                         // [2 halves][ACT][32]
-constexpr int LDS_B2 = LDS_K2 + 2 * ACT * 32;               // [ACT] + 1 pad
-constexpr int LDS_FLOATS = LDS_B2 + 4;
-constexpr int BLOB_FLOATS = OFF_LDS + LDS_FLOATS;
-static_assert(OFF_LDS % 4 == 0 && LDS_FLOATS % 4 == 0 && BLOB_FLOATS % 4 == 0, "the LDS part is copied as float4 and every slot stays 16-byte aligned");
 
 struct BankArgs {
     const float* bank;
@@ -88,7 +63,6 @@ __device__ __forceinline__ int64_t uniform(int64_t v)
 template <bool RAW, bool EPS>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qbank_kernel(const BankArgs a)
 {
-#pragma clang fp contract(off)
     // a copy of the LDS part per wavefront: the network is a property of the wavefront's item, not of the block
     __shared__ float4 lds_all[WAVES][LDS_FLOATS / 4];
 
@@ -96,7 +70,6 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qbank_kernel(const Bank
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, col = lane & 31;
     float4* const lds4 = lds_all[wave];
-    const float* const lds = reinterpret_cast<const float*>(lds4);
 
     uint64_t tick = a.tick;
     if constexpr (EPS) {
@@ -123,14 +96,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qbank_kernel(const Bank
         if (p != loaded) {
             loaded = p;
             const float* const blob = a.bank + p * BLOB_FLOATS;
-#pragma unroll
-            for (int st = 0; st < K1_STEPS; ++st)
-#pragma unroll
-                for (int M = 0; M < 2; ++M) w1[st][M] = blob[OFF_W1 + (st * 2 + M) * 64 + lane];
-#pragma unroll
-            for (int M = 0; M < 2; ++M)
-#pragma unroll
-                for (int st = 0; st < K2_STEPS; ++st) w2[M][st] = blob[OFF_W2 + (M * K2_STEPS + st) * 64 + lane];
+            load_operands(blob, lane, w1, w2);
             const float4* const blob4 = reinterpret_cast<const float4*>(blob + OFF_LDS);
             wave_sync_lds();                                  // the reads of the previous network's copy are done
             static_assert(LDS_FLOATS / 4 > 64 && LDS_FLOATS / 4 <= 128, "two float4 per lane cover the LDS part");
@@ -151,111 +117,14 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void qbank_kernel(const Bank
         const float* const xin = a.in + (h != 0 ? a.ld : 0) + i;
 #pragma unroll
         for (int st = 0; st < K1_STEPS; ++st) x[st] = (live && 2 * st + h < IN) ? xin[2 * st * a.ld] : 0.0f;
-#pragma unroll
-        for (int st = 0; st < K1_STEPS; ++st) {
-            // AquaStateNormalizer as the step kernels' epilogue writes it: a rounded float32 before the layer sees it
-            // (0 stays 0 on the padding row and on dead worlds, except for the angle's 0.5 which meets a zero weight or no store)
-            if constexpr (RAW) x[st] = (2 * st + h == 2) ? fmaf(x[st], 0.15915494309189535f, 0.5f) : x[st] * 0.01f;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-
-        f32x16 h1[2], h2[2];
-#pragma unroll
-        for (int M = 0; M < 2; ++M)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 b0 = lds4[(LDS_B0 + h * 32 + M * 16) / 4 + g], b1 = lds4[(LDS_B1 + h * 32 + M * 16) / 4 + g];
-                h1[M][4 * g + 0] = b0.x; h1[M][4 * g + 1] = b0.y; h1[M][4 * g + 2] = b0.z; h1[M][4 * g + 3] = b0.w;
-                h2[M][4 * g + 0] = b1.x; h2[M][4 * g + 1] = b1.y; h2[M][4 * g + 2] = b1.z; h2[M][4 * g + 3] = b1.w;
-            }
-
-        // (scheduling fences in front of the two MFMA layers, as in qpolicy_kernel: they keep the LDS reads of the three
-        // layers from being hoisted to the top of the tile, which would not fit 170 registers)
-        __builtin_amdgcn_sched_barrier(0);
-        // layer 1: 64 x 5
-#pragma unroll
-        for (int st = 0; st < K1_STEPS; ++st)
-#pragma unroll
-            for (int M = 0; M < 2; ++M) h1[M] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st][M], x[st], h1[M], 0, 0, 0);
-
-        __builtin_amdgcn_sched_barrier(0);
-        // layer 2: 64 x 64.  k-step (M, r): B is this lane's own h1[M][r]
-#pragma unroll
-        for (int M = 0; M < 2; ++M)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float b = fmaxf(h1[M][r], 0.0f);
-                h2[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[0][M * 16 + r], b, h2[0], 0, 0, 0);
-                h2[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[1][M * 16 + r], b, h2[1], 0, 0, 0);
-            }
-
-        // layer 3: 3 x 64 on the VALU from the 32 units this lane holds, then one add across the lane halves
-        float pq[ACT];
-#pragma unroll
-        for (int c = 0; c < ACT; ++c) pq[c] = h == 0 ? lds[LDS_B2 + c] : 0.0f;
-#pragma unroll
-        for (int M = 0; M < 2; ++M)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float v0 = fmaxf(h2[M][4 * g + 0], 0.0f), v1 = fmaxf(h2[M][4 * g + 1], 0.0f);
-                const float v2 = fmaxf(h2[M][4 * g + 2], 0.0f), v3 = fmaxf(h2[M][4 * g + 3], 0.0f);
-#pragma unroll
-                for (int c = 0; c < ACT; ++c) {
-                    const float4 k = lds4[(LDS_K2 + (h * ACT + c) * 32 + M * 16) / 4 + g];
-                    pq[c] = fmaf(k.x, v0, pq[c]);
-                    pq[c] = fmaf(k.y, v1, pq[c]);
-                    pq[c] = fmaf(k.z, v2, pq[c]);
-                    pq[c] = fmaf(k.w, v3, pq[c]);
-                }
-            }
         float q[ACT];
-#pragma unroll
-        for (int c = 0; c < ACT; ++c) q[c] = pq[c] + __shfl_xor(pq[c], 32);      // the same bits on both halves
-
-        if (h == 0 && live) {
-            int act = 0;                                      // np.argmax: the lowest index on a tie
-            float best = q[0];
-            if (q[1] > best) { act = 1; best = q[1]; }
-            if (q[2] > best) { act = 2; best = q[2]; }
-            if constexpr (EPS) {
-                uint32_t r[4];
-                draw(a.seed, static_cast<uint64_t>(a.env_offset + i), tick, STREAM_POLICY, 0, r);
-                if (u_01(r[0]) < eps) act = static_cast<int>(random_action(r));
-            }
-            if (a.action != nullptr) a.action[i] = static_cast<uint8_t>(act);
-            if (a.q != nullptr) {
-#pragma unroll
-                for (int c = 0; c < ACT; ++c) a.q[c * a.q_ld + i] = q[c];
-            }
-            if (a.q_taken != nullptr) a.q_taken[i] = act == 0 ? q[0] : (act == 1 ? q[1] : q[2]);
-        }
+        forward<RAW>(lds4, w1, w2, x, h, q);
+        if (h == 0 && live)
+            pick_and_store<EPS>(q[0], q[1], q[2], eps, a.seed, static_cast<uint64_t>(a.env_offset + i), tick, i, a.action, a.q, a.q_ld, a.q_taken);
     }
 }
 
 // ------------------------------------------------------------------ host side
-// compute units of a device, asked once (an attribute query is no stream operation: legal under capture)
-constexpr int MAX_DEVICES = 64;
-std::atomic<int> g_cus[MAX_DEVICES];
-
-int compute_units(int* out)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(AQUABANK_E_NODEVICE, "no HIP device: %s", hipGetErrorString(e));
-    }
-    int cus = (dev >= 0 && dev < MAX_DEVICES) ? g_cus[dev].load(std::memory_order_relaxed) : 0;
-    if (cus <= 0) {
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute");
-        if (cus <= 0) cus = 1;
-        if (dev >= 0 && dev < MAX_DEVICES) g_cus[dev].store(cus, std::memory_order_relaxed);
-    }
-    *out = cus;
-    return 0;
-}
-
 // The items of a launch: the tiles that hold a world below N, so the work follows N however large seg is.  Every network
 // but the last one with a world has all its `tiles`; the last one, which N may cut, has those of its n_last worlds.  Item
 // t is still (network t / tiles, tile t % tiles), because only the last network is short.
@@ -291,28 +160,8 @@ int aquabank_unpack_weights(const void* blob_host, float* k0, float* b0, float* 
         return fail(AQUABANK_E_INVALID, "a kernel or bias pointer is NULL");
     if (!aligned(blob_host, 4)) return fail(AQUABANK_E_ALIGN, "blob must be 4-byte aligned");
     const float* const w = static_cast<const float*>(blob_host);
-    for (int lane = 0; lane < 64; ++lane) {
-        const int h = lane >> 5, i = lane & 31;
-        for (int s = 0; s < K1_STEPS; ++s)
-            for (int M = 0; M < 2; ++M) {
-                const int k = 2 * s + h;                                  // input of this k-step and lane half
-                if (k < IN) k0[k * HID + 32 * M + i] = w[OFF_W1 + (s * 2 + M) * 64 + lane];
-            }
-        for (int M2 = 0; M2 < 2; ++M2)                                    // row block of the OUTPUT unit 32 M2 + i
-            for (int M = 0; M < 2; ++M)
-                for (int r = 0; r < 16; ++r)                              // k-step: the input unit register r of block M holds
-                    k1[unit_of(M, r, h) * HID + 32 * M2 + i] = w[OFF_W2 + (M2 * K2_STEPS + M * 16 + r) * 64 + lane];
-    }
-    const float* const l = w + OFF_LDS;
-    for (int h = 0; h < 2; ++h)
-        for (int M = 0; M < 2; ++M)
-            for (int r = 0; r < 16; ++r) {
-                const int u = unit_of(M, r, h);
-                b0[u] = l[LDS_B0 + h * 32 + M * 16 + r];
-                b1[u] = l[LDS_B1 + h * 32 + M * 16 + r];
-                for (int c = 0; c < ACT; ++c) k2[u * ACT + c] = l[LDS_K2 + (h * ACT + c) * 32 + M * 16 + r];
-            }
-    for (int c = 0; c < ACT; ++c) b2[c] = l[LDS_B2 + c];
+    float* const dst[6] = {k0, b0, k1, b1, k2, b2};
+    for_each_parameter([&](int b, int a, int i) { dst[a][i] = w[b]; });
     return 0;
 }
 
@@ -343,7 +192,7 @@ int aquabank_act_f32(const void* bank_dev, int64_t networks, int64_t seg, const 
     if (N == 0) return 0;
 
     int cus = 0;
-    if (const int rc = compute_units(&cus)) return rc;
+    if (const int rc = compute_units(&cus, AQUABANK_E_NODEVICE)) return rc;
     BankArgs a;
     a.seg = seg;
     a.tiles = seg / TILE + (seg % TILE != 0 ? 1 : 0);

@@ -1,6 +1,6 @@
 """CPU-only checks of libaqua_bank.so (include/aqua_bank.h), the bank of Q-networks: it builds and loads, exports what its
 header declares and leaves the other six libraries alone, has a build-table entry of its own behind the pinned tables,
-restates the policy library's blob layout correctly (pinned against the real packer through aquabank_unpack_weights),
+shares the policy library's blob layout (one statement in csrc/aqua_qnet.hpp; aquabank_unpack_weights inverts the real packer),
 rejects bad arguments before touching a device, keeps the hidden layer on v_mfma_f32_32x32x2_f32 without scratch or spills
 within three wavefronts per SIMD, and has no CPU path."""
 import ctypes
@@ -104,9 +104,14 @@ def test_graft_entry_builds_and_checks_the_new_library():
     assert "every_library()" in text and "_bank_capi" in text and "aquabank_version" in text
 
 
-def test_restated_layout_is_the_packers(bcapi, pcapi):
-    """aquapol_pack_weights -> aquabank_unpack_weights returns every array bit for bit, and what unpack does not read is 0:
-    the layout constants aqua_bank.hip restates are those of aqua_policy.hip"""
+def test_pack_and_unpack_are_inverse_through_the_shared_map(bcapi, pcapi):
+    """aquapol_pack_weights in one library and aquabank_unpack_weights in the other apply the one index map of
+    csrc/aqua_qnet.hpp in opposite directions: every array comes back bit for bit, the padding floats are written as 0 by
+    pack and never read by unpack, and the layout and the device query are stated once under csrc/"""
+    csrc = os.path.join(ROOT, "aquaticgymenv_amd", "csrc")
+    texts = {name: open(os.path.join(csrc, name)).read() for name in sorted(os.listdir(csrc))}
+    for once in ("constexpr int OFF_W1", "int compute_units("):
+        assert {name: t.count(once) for name, t in texts.items() if once in t} == {"aqua_qnet.hpp": 1}, once
     nbytes = bcapi.lib.aquabank_weights_bytes()
     assert nbytes == pcapi.lib.aquapol_weights_bytes() == 19216 and nbytes % 16 == 0
     shapes = ((5, 64), (64, 64), (64, 3))

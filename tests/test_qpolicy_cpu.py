@@ -90,7 +90,7 @@ def test_packing_is_deterministic_and_sized(pcapi):
 
 
 def _emulate(blob, x):
-    """The kernel re-stated lane by lane in int64 from the BLOB alone (aqua_policy.hip's layout comment): worlds on the
+    """The kernel re-stated lane by lane in int64 from the BLOB alone (aqua_qnet.hpp's layout comment): worlds on the
     MFMA's column index, units on its rows, accumulator register r of lane half h = row (r & 3) + 8 (r >> 2) + 4 h,
     A operand lane l = A[l & 31][k = l >> 5], B operand lane l = B[k = l >> 5][l & 31].  x: int [5][32] -> q int64 [3][32]."""
     f = blob.view(np.float32).astype(np.int64)
@@ -213,8 +213,13 @@ def test_codegen_keeps_the_hidden_layer_on_the_f32_mfma_without_scratch(isa):
 def test_committed_isa_record_is_of_this_source():
     with open(os.path.join(ROOT, "profiles", "isa_budget.json")) as f:
         row = json.load(f)["qpolicy"]
-    with open(os.path.join(ROOT, "aquaticgymenv_amd", "csrc", "aqua_policy.hip"), "rb") as f:
-        assert row["source_sha16"] == hashlib.sha256(f.read()).hexdigest()[:16], "run tools/make_policy_isa_budget.py"
+    from aquaticgymenv_amd import build
+    h = hashlib.sha256()                               # the kernel's body is in aqua_qnet.hpp: every dependency, in table order
+    for dep in build.POLICY_DEPS:
+        with open(dep, "rb") as f:
+            h.update(f.read())
+    assert row["source_sha16"] == h.hexdigest()[:16], "run tools/make_policy_isa_budget.py"
+    assert row["source"] == [os.path.relpath(dep, ROOT) for dep in build.POLICY_DEPS] and len(row["source"]) == 5
     assert len(row["kernels"]) == 4
     for k in row["kernels"].values():
         assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["occupancy_waves_per_simd"] >= 3
