@@ -35,7 +35,7 @@ def _library(name, headers):
 LIBRARIES = {
     "hip": _library("hip", ["aqua_device.hpp", "aqua_tuning.inc"]),
     "policy": _library("policy", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
-    "learner": _library("learner", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+    "learner": _library("learner", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp", "aqua_lrn.hpp"]),
     "episodes": _library("episodes", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
 }
 # Libraries added since, in build order behind the four above (whose table, order and command lines are pinned).
@@ -53,11 +53,17 @@ ADDON_LIBRARIES = {
 BANK_LIBRARIES = {
     "bank": _library("bank", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
 }
+# Libraries behind those (the four tables above and what each_library() returns are pinned as well).
+# lbank: the learner bank, one DQN update of every network of a bank in two launches (include/aqua_lbank.h); its device
+# code is the learner's, stated once in aqua_lrn.hpp.
+POPULATION_LIBRARIES = {
+    "lbank": _library("lbank", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp", "aqua_lrn.hpp"]),
+}
 
 
 def library(name):
-    """the table entry of library `name`, from LIBRARIES, EXTRA_LIBRARIES, ADDON_LIBRARIES or BANK_LIBRARIES"""
-    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES):
+    """the table entry of library `name`, from any of the five tables"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -74,8 +80,13 @@ def every_library():
 
 
 def each_library():
-    """every library's name, those of BANK_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    """every library's name up to BANK_LIBRARIES, in build order"""
     return every_library() + list(BANK_LIBRARIES)
+
+
+def libraries():
+    """all eight libraries' names, those of POPULATION_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return each_library() + list(POPULATION_LIBRARIES)
 
 
 def hipcc_path():
@@ -126,6 +137,8 @@ REPLAY_SRC, REPLAY_DEPS, REPLAY_LIB, REPLAY_FLAGS = (ADDON_LIBRARIES["replay"][k
 build_replay, replay_needs_build = functools.partial(build_library, "replay"), functools.partial(needs_build, "replay")
 BANK_SRC, BANK_DEPS, BANK_LIB, BANK_FLAGS = (BANK_LIBRARIES["bank"][k] for k in ("src", "deps", "lib", "flags"))
 build_bank, bank_needs_build = functools.partial(build_library, "bank"), functools.partial(needs_build, "bank")
+LBANK_SRC, LBANK_DEPS, LBANK_LIB, LBANK_FLAGS = (POPULATION_LIBRARIES["lbank"][k] for k in ("src", "deps", "lib", "flags"))
+build_lbank, lbank_needs_build = functools.partial(build_library, "lbank"), functools.partial(needs_build, "lbank")
 
 
 def build_variant(name, flags, verbose=False):
@@ -175,5 +188,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in each_library():
+    for name in libraries():
         print(build_library(name, force="--force" in sys.argv, verbose=True))

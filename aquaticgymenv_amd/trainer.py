@@ -157,3 +157,116 @@ class DQNLoop(object):
         g._loop = self                                        # the buffers the graph's nodes point at
         g.done_history = None
         return g
+
+
+class PopulationLoop(DQNLoop):
+    """One iteration of P trainings on ONE batch of worlds as one chain of launches: the networks of a QNetworkBank act on
+    their segments of the batch, the one ring records the step, and a DQNLearnerBank (lbank.py) draws every network's
+    minibatch from its own slots and updates every network.  In stream order:
+
+        1. bank act with the bank's device epsilon array, keyed by the device tick base
+        2. ring open: (s, a, ok)                      5. tracker.after_step()               (two launches)
+        3. step launch                                6. bank draw: idx [P][B] of the updates t_p -> t_p + 1
+        4. ring close: (r, s', d)                     7. bank update                        (two launches)
+                                                      8. tick advance
+
+    Ten kernels.  step() queues them eagerly; capture().launch() replays them as ONE graph (DQNLoop's capture).  Network p
+    explores with bank.epsilon[p], the caller's device array: the graph reads whatever it holds when it runs (a per-network
+    schedule on the device is not part of this).  The tracker's log names the world of every episode, so the success rate of
+    network p is that of the records with log_world // bank.seg == p.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64):
+        """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
+        array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
+        of env.num_envs; tracker: an EpisodeTracker of env.  Everything on one device; anything else is a ValueError."""
+        from . import _lbank_capi
+        if env.continuous:
+            raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
+        if env.obs_norm_buf is None:
+            raise ValueError("the ring stores the normalised observation: construct the env with normalized_obs=True")
+        if not hasattr(bank, "networks") or not getattr(bank, "_aquapol_network", False):
+            raise ValueError("expected a QNetworkBank")
+        if getattr(learners, "bank", None) is not bank:
+            raise ValueError("the learner bank trains another bank than the one that acts")
+        if bank.epsilon is None:
+            raise ValueError("set bank.epsilon to a float32 [networks] device tensor: every network explores with its own entry")
+        if getattr(ring, "header", None) is None or ring.env is not env:
+            raise ValueError("expected a DeviceReplayRing of this env")
+        if tracker.env is not env:
+            raise ValueError("expected an EpisodeTracker of this env")
+        for what, dev in (("bank", bank.device), ("learner bank", learners.device), ("ring", ring.device), ("tracker", tracker.device)):
+            if dev != env.device:
+                raise ValueError("the environment is on %s, the %s on %s" % (env.device, what, dev))
+        if ring.capacity % env.num_envs != 0:
+            raise ValueError("the ring's capacity (%d) must be a multiple of the batch (%d worlds): a slot then belongs to one world, "
+                             "and so to one network" % (ring.capacity, env.num_envs))
+        if bank.seg * bank.networks < env.num_envs:
+            raise ValueError("%d networks x %d worlds do not cover the batch of %d" % (bank.networks, bank.seg, env.num_envs))
+        B = int(batch_size)
+        if B < 1 or B > _lbank_capi.MAX_BATCH:
+            raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _lbank_capi.MAX_BATCH))
+        self.env, self.bank, self.learners, self.ring, self.tracker, self.batch_size = env, bank, learners, ring, tracker, B
+        self.qnet = bank                                      # (what DQNLoop.capture() hands to the graph as its policy)
+        self.torch = env.torch
+        self.view = ring.learner_view()
+        self.idx = self.torch.full((bank.networks, B), -1, dtype=self.torch.int32, device=env.device)
+        env.policy_action                                     # (allocated here, not inside a capture)
+        learners._grow(B)
+
+    def _act(self, s):
+        from . import _bank_capi
+        env = self.env
+        _bank_capi.check(env._policy_launch(self.bank, 0.0, 0, env._tick_dev.data_ptr(), s), "aquabank_act_f32")
+
+    def _queue(self):
+        """the eight stages on torch's current stream, every draw keyed by the device tick base or the update counters"""
+        env, ring = self.env, self.ring
+        action, tb = env.policy_action, env._tick_dev
+        s = env._stream()
+        self._act(s)
+        ring.before_step(action)
+        _capi.check(env._step_launch(action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
+                                     env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
+        ring.after_step()
+        self.tracker.after_step()
+        self.learners.draw(ring, self.batch_size, out=self.idx)
+        self.learners.update(self.view, self.batch_size, self.idx)
+        _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
+
+    def _warm_up(self):
+        """DQNLoop._warm_up's rule: every kernel of the iteration runs once, on the current stream, and leaves no trace.  The
+        bank writes policy_action (an output); the accounting sees a batch in which no world counts; the ring kernels and the
+        bank draw run on a one-slot scratch ring; the learner bank gets minibatches without a sample (documented to leave
+        everything but loss and grad as it was, and those are put back); the step is taken on a snapshot and taken back."""
+        from . import _lbank_capi
+        torch, env, tracker, learners = self.torch, self.env, self.tracker, self.learners
+        dev, n = env.device, env.num_envs
+        rpl = self.ring._capi
+        s = env._stream()
+        tb = env._tick_dev
+        self._act(s)
+        tracker.after_step(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
+                           torch.full((n,), -1, dtype=torch.int32, device=dev))
+        header = torch.zeros(rpl.HEADER_WORDS, dtype=torch.int64, device=dev)
+        rows = torch.zeros((5, 1), dtype=torch.float32, device=dev)
+        f32, u8 = torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.uint8, device=dev)
+        idx = torch.full_like(self.idx, -1)
+        rpl.check(rpl.lib.aquarpl_open(header.data_ptr(), rows.data_ptr(), u8[0:].data_ptr(), u8[1:].data_ptr(), 1, 1, rows.data_ptr(), 1,
+                                       u8[2:].data_ptr(), rpl.ACT_U8, 1, None, 1, s), "aquarpl_open")
+        rpl.check(rpl.lib.aquarpl_close(header.data_ptr(), f32.data_ptr(), rows.data_ptr(), u8[0:].data_ptr(), 1, 1, f32.data_ptr(),
+                                        rows.data_ptr(), 1, u8[2:].data_ptr(), 1, s), "aquarpl_close")
+        _lbank_capi.check(_lbank_capi.lib.aqualbank_draw(header.data_ptr(), u8[1:].data_ptr(), 1, 1, 1, learners.networks,
+                                                         learners.t.data_ptr(), learners.seed_dev.data_ptr(), idx.data_ptr(),
+                                                         self.batch_size, s), "aqualbank_draw")
+        idx.fill_(-1)
+        loss = learners.loss.clone()
+        grad = learners.grad.clone()
+        learners.update(self.view, self.batch_size, idx)                     # no sample: nothing but loss and grad is written
+        learners.loss.copy_(loss)
+        learners.grad.copy_(grad)
+        snap = env.snapshot()
+        _capi.check(env._step_launch(env.policy_action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
+                                     env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
+        env.restore(snap)
+        _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 0, s), "aqua_tick_advance")
+        torch.cuda.current_stream(dev).synchronize()

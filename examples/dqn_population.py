@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""P DQN trainings with different learning rates and discounts on ONE batch of worlds, entirely on the device: what
+main/impl/dqn.py:11-13 prepares for ("to allow multiple trainings in parallel") as one captured graph.
+
+Network p of a QNetworkBank acts in worlds [p * seg, (p + 1) * seg) (libaqua_bank.so); one batched step moves every world;
+the transitions of all networks land in the one device experience ring; DQNLearnerBank (libaqua_lbank.so) draws every
+network's minibatch from its own slots of that ring and updates all P networks in two launches.  The whole iteration is
+trainer.PopulationLoop: ten kernels, one graph launch from Python.
+
+Exploration: network p explores with eps[p], a device array the graph reads.  It is refreshed from the host every
+--refresh iterations from the episodes each network has finished (dqn.py:184 decays once per finished episode).  The
+per-network success rate comes from the tracker's log, whose records name their world: network = log_world // seg.
+
+    python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles]
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+from aquaticgymenv_amd.batched import BatchedAqua
+from aquaticgymenv_amd.episodes import EpisodeTracker
+from aquaticgymenv_amd.lbank import DQNLearnerBank
+from aquaticgymenv_amd.qbank import QNetworkBank
+from aquaticgymenv_amd.replay import DeviceReplayRing
+from aquaticgymenv_amd.trainer import PopulationLoop
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--networks", type=int, default=8)
+ap.add_argument("--seg", type=int, default=256, help="worlds per network")
+ap.add_argument("--steps", type=int, default=3000)
+ap.add_argument("--batch", type=int, default=64, help="samples per network and update (the reference: 64)")
+ap.add_argument("--rounds", type=int, default=256, help="batched steps the ring holds (its capacity is rounds x worlds)")
+ap.add_argument("--obstacles", action="store_true")
+ap.add_argument("--epsilon-decay", type=float, default=10000, help="episodes of a network to reach the final epsilon")
+ap.add_argument("--refresh", type=int, default=50, help="iterations between two refreshes of the epsilon array")
+ap.add_argument("--seed", type=int, default=0)
+args = ap.parse_args()
+
+EPS_INIT, EPS_FINAL, TAU = 1.0, 0.05, 0.005                   # default_hyperparam of dqn.py
+P, seg = args.networks, args.seg
+worlds = P * seg
+# the sweep: learning rates a factor 10 around dqn.py's 1e-3, discounts between 0.9 and 0.99
+lrs = [1e-3 * 10.0 ** ((p % 4 - 1.5) / 3.0) for p in range(P)]
+gammas = [0.9 + 0.09 * (p // 4) / max((P - 1) // 4, 1) for p in range(P)]
+
+rng = np.random.RandomState(args.seed)
+networks = []
+for p in range(P):                                             # Keras' default: Glorot-uniform kernels, zero biases
+    layers = []
+    for fan_in, fan_out in ((5, 64), (64, 64), (64, 3)):
+        lim = np.sqrt(6.0 / (fan_in + fan_out))
+        layers.append((rng.uniform(-lim, lim, (fan_in, fan_out)).astype(np.float32), np.zeros(fan_out, dtype=np.float32)))
+    networks.append(layers)
+bank = QNetworkBank(networks, seg, "cuda")
+eps = torch.full((P,), EPS_INIT, dtype=torch.float32, device=bank.device)
+bank.epsilon = eps
+learners = DQNLearnerBank(bank, gamma=gammas, tau=TAU, lr=lrs, strategy="double_ref", seed=args.seed)
+
+env = BatchedAqua(worlds, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
+env.reset()
+ring = DeviceReplayRing(env, capacity=args.rounds * worlds)   # a multiple of the batch: a slot belongs to one world
+tracker = EpisodeTracker(env)
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch).capture()
+decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
+episodes, seen = np.zeros(P, dtype=np.int64), 0               # finished episodes per network, and in all
+for step in range(1, args.steps + 1):
+    graph.launch()                                             # act, record, step, record, account, draw, update, tick
+    if step % args.refresh == 0:                               # host reads: the new records, then P floats back to the device
+        total = tracker.counts()["episodes"]
+        new = tracker.last(total - seen)                       # (at most the log's capacity of them)
+        episodes += np.bincount(new["world"] // seg, minlength=P)[:P]
+        seen = total
+        eps.copy_(torch.from_numpy(np.maximum(EPS_FINAL, EPS_INIT * decay ** episodes).astype(np.float32)))
+    if step % 100 == 0:
+        log = tracker.last(tracker.capacity)
+        owner = log["world"] // seg
+        loss = learners.loss.cpu().numpy()
+        print("step %6d  episodes %7d  ring %d" % (step, tracker.counts()["episodes"], ring.filled()))
+        for p in range(P):
+            mine = np.nonzero(owner == p)[0][-100:]
+            k = max(mine.size, 1)
+            print("    network %3d  lr %.2e  gamma %.3f  epsilon %.3f  last %3d episodes: reward %8.2f  success %3.0f %%  loss %10.4f" %
+                  (p, lrs[p], gammas[p], float(eps[p]), mine.size, float(log["ret"][mine].sum()) / k,
+                   100.0 * float((log["code"][mine] == 3).sum()) / k, float(loss[p])))
+for p in range(P):
+    learners.weights(p)                                        # bank.layers[p] now holds the trained network p

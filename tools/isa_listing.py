@@ -1,7 +1,7 @@
 """The device assembly of one of the project's HIP libraries and its kernels, as the compiler reports them (no GPU
 needed).  tools/make_policy_isa_budget.py, tools/learner_isa.py and tools/episodes_isa.py print it; tests/test_qpolicy_cpu.py,
-tests/test_learner_cpu.py, tests/test_episodes_cpu.py, tests/test_replay_cpu.py and tests/test_qbank_cpu.py gate the same
-listing.
+tests/test_learner_cpu.py, tests/test_episodes_cpu.py, tests/test_replay_cpu.py, tests/test_qbank_cpu.py and
+tests/test_lbank_cpu.py gate the same listing.
 """
 import os
 import re
