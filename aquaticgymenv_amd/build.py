@@ -61,9 +61,17 @@ POPULATION_LIBRARIES = {
 }
 
 
+# Libraries behind those (the five tables above and what libraries() returns are pinned as well).
+# segments: per-segment episode counters, epsilon schedules and windowed statistics from the episode log
+# (include/aqua_segments.h).
+SEGMENT_LIBRARIES = {
+    "segments": _library("segments", ["aqua_host.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the five tables"""
-    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES):
+    """the table entry of library `name`, from any of the six tables"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -85,8 +93,13 @@ def each_library():
 
 
 def libraries():
-    """all eight libraries' names, those of POPULATION_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    """the eight libraries' names up to POPULATION_LIBRARIES, in build order"""
     return each_library() + list(POPULATION_LIBRARIES)
+
+
+def nine_libraries():
+    """all nine libraries' names, those of SEGMENT_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return libraries() + list(SEGMENT_LIBRARIES)
 
 
 def hipcc_path():
@@ -139,6 +152,8 @@ BANK_SRC, BANK_DEPS, BANK_LIB, BANK_FLAGS = (BANK_LIBRARIES["bank"][k] for k in 
 build_bank, bank_needs_build = functools.partial(build_library, "bank"), functools.partial(needs_build, "bank")
 LBANK_SRC, LBANK_DEPS, LBANK_LIB, LBANK_FLAGS = (POPULATION_LIBRARIES["lbank"][k] for k in ("src", "deps", "lib", "flags"))
 build_lbank, lbank_needs_build = functools.partial(build_library, "lbank"), functools.partial(needs_build, "lbank")
+SEGMENTS_SRC, SEGMENTS_DEPS, SEGMENTS_LIB, SEGMENTS_FLAGS = (SEGMENT_LIBRARIES["segments"][k] for k in ("src", "deps", "lib", "flags"))
+build_segments, segments_needs_build = functools.partial(build_library, "segments"), functools.partial(needs_build, "segments")
 
 
 def build_variant(name, flags, verbose=False):
@@ -188,5 +203,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in libraries():
+    for name in nine_libraries():
         print(build_library(name, force="--force" in sys.argv, verbose=True))

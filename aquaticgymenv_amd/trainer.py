@@ -171,14 +171,21 @@ class PopulationLoop(DQNLoop):
                                                       8. tick advance
 
     Ten kernels.  step() queues them eagerly; capture().launch() replays them as ONE graph (DQNLoop's capture).  Network p
-    explores with bank.epsilon[p], the caller's device array: the graph reads whatever it holds when it runs (a per-network
-    schedule on the device is not part of this).  The tracker's log names the world of every episode, so the success rate of
-    network p is that of the records with log_world // bank.seg == p.  There is no CPU path."""
+    explores with bank.epsilon[p], the caller's device array: the graph reads whatever it holds when it runs.  The tracker's
+    log names the world of every episode, so the success rate of network p is that of the records with
+    log_world // bank.seg == p.
 
-    def __init__(self, env, bank, learners, ring, tracker, batch_size=64):
+    With segments=, a SegmentTracker (segments.py) of this tracker whose epsilon array IS bank.epsilon, stage 5 is followed by
+    its launch: every network's schedule advances by the episodes its worlds finished in this step (dqn.py:184), and its
+    counters and windowed statistics follow, on the device.  Eleven kernels, and no host read is needed to keep the loop
+    correct.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
-        of env.num_envs; tracker: an EpisodeTracker of env.  Everything on one device; anything else is a ValueError."""
+        of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
+        bank's segment size and number of networks, whose epsilon is bank.epsilon.  Everything on one device; anything else
+        is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
@@ -202,10 +209,19 @@ class PopulationLoop(DQNLoop):
                              "and so to one network" % (ring.capacity, env.num_envs))
         if bank.seg * bank.networks < env.num_envs:
             raise ValueError("%d networks x %d worlds do not cover the batch of %d" % (bank.networks, bank.seg, env.num_envs))
+        if segments is not None:
+            if getattr(segments, "tracker", None) is not tracker:
+                raise ValueError("expected a SegmentTracker of this EpisodeTracker")
+            if segments.epsilon is None or segments.epsilon is not bank.epsilon:
+                raise ValueError("set bank.epsilon = segments.epsilon: the bank explores with the schedules the SegmentTracker advances")
+            if segments.seg != bank.seg or segments.segments != bank.networks:
+                raise ValueError("the SegmentTracker has %d segments of %d worlds, the bank %d networks of %d" %
+                                 (segments.segments, segments.seg, bank.networks, bank.seg))
         B = int(batch_size)
         if B < 1 or B > _lbank_capi.MAX_BATCH:
             raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _lbank_capi.MAX_BATCH))
         self.env, self.bank, self.learners, self.ring, self.tracker, self.batch_size = env, bank, learners, ring, tracker, B
+        self.segments = segments
         self.qnet = bank                                      # (what DQNLoop.capture() hands to the graph as its policy)
         self.torch = env.torch
         self.view = ring.learner_view()
@@ -229,6 +245,8 @@ class PopulationLoop(DQNLoop):
                                      env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
         ring.after_step()
         self.tracker.after_step()
+        if self.segments is not None:
+            self.segments.account()
         self.learners.draw(ring, self.batch_size, out=self.idx)
         self.learners.update(self.view, self.batch_size, self.idx)
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
@@ -236,8 +254,9 @@ class PopulationLoop(DQNLoop):
     def _warm_up(self):
         """DQNLoop._warm_up's rule: every kernel of the iteration runs once, on the current stream, and leaves no trace.  The
         bank writes policy_action (an output); the accounting sees a batch in which no world counts; the ring kernels and the
-        bank draw run on a one-slot scratch ring; the learner bank gets minibatches without a sample (documented to leave
-        everything but loss and grad as it was, and those are put back); the step is taken on a snapshot and taken back."""
+        bank draw run on a one-slot scratch ring; the SegmentTracker, if there is one, finds no new record; the learner bank
+        gets minibatches without a sample (documented to leave everything but loss and grad as it was, and those are put
+        back); the step is taken on a snapshot and taken back."""
         from . import _lbank_capi
         torch, env, tracker, learners = self.torch, self.env, self.tracker, self.learners
         dev, n = env.device, env.num_envs
@@ -247,6 +266,8 @@ class PopulationLoop(DQNLoop):
         self._act(s)
         tracker.after_step(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
                            torch.full((n,), -1, dtype=torch.int32, device=dev))
+        if self.segments is not None:
+            self.segments.account()                                          # no new record: its cursor is the log's already
         header = torch.zeros(rpl.HEADER_WORDS, dtype=torch.int64, device=dev)
         rows = torch.zeros((5, 1), dtype=torch.float32, device=dev)
         f32, u8 = torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.uint8, device=dev)

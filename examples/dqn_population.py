@@ -5,13 +5,17 @@ main/impl/dqn.py:11-13 prepares for ("to allow multiple trainings in parallel") 
 Network p of a QNetworkBank acts in worlds [p * seg, (p + 1) * seg) (libaqua_bank.so); one batched step moves every world;
 the transitions of all networks land in the one device experience ring; DQNLearnerBank (libaqua_lbank.so) draws every
 network's minibatch from its own slots of that ring and updates all P networks in two launches.  The whole iteration is
-trainer.PopulationLoop: ten kernels, one graph launch from Python.
+trainer.PopulationLoop: eleven kernels, one graph launch from Python.
 
-Exploration: network p explores with eps[p], a device array the graph reads.  It is refreshed from the host every
---refresh iterations from the episodes each network has finished (dqn.py:184 decays once per finished episode).  The
-per-network success rate comes from the tracker's log, whose records name their world: network = log_world // seg.
+Exploration: network p explores with eps[p], a device array the graph reads and a SegmentTracker (libaqua_segments.so)
+advances inside the graph: once per episode the network's worlds finish, as dqn.py:184 does.  The same launch keeps every
+network's mean reward and success rate over its last 100 episodes (dqn.py:196-198) on the device.  Nothing is read back
+between two prints, and a print reads P numbers of each.
 
-    python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles]
+--host-refresh keeps the loop as it was before that library: ten kernels, eps refreshed from the host every --refresh
+iterations from the tracker's log, the statistics rebuilt on the host from the log.
+
+    python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
 """
 import argparse
 import os
@@ -26,6 +30,7 @@ from aquaticgymenv_amd.episodes import EpisodeTracker
 from aquaticgymenv_amd.lbank import DQNLearnerBank
 from aquaticgymenv_amd.qbank import QNetworkBank
 from aquaticgymenv_amd.replay import DeviceReplayRing
+from aquaticgymenv_amd.segments import SegmentTracker
 from aquaticgymenv_amd.trainer import PopulationLoop
 
 ap = argparse.ArgumentParser()
@@ -36,7 +41,8 @@ ap.add_argument("--batch", type=int, default=64, help="samples per network and u
 ap.add_argument("--rounds", type=int, default=256, help="batched steps the ring holds (its capacity is rounds x worlds)")
 ap.add_argument("--obstacles", action="store_true")
 ap.add_argument("--epsilon-decay", type=float, default=10000, help="episodes of a network to reach the final epsilon")
-ap.add_argument("--refresh", type=int, default=50, help="iterations between two refreshes of the epsilon array")
+ap.add_argument("--host-refresh", action="store_true", help="the schedule and the statistics on the host, as before the SegmentTracker")
+ap.add_argument("--refresh", type=int, default=50, help="with --host-refresh: iterations between two refreshes of the epsilon array")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 
@@ -56,35 +62,47 @@ for p in range(P):                                             # Keras' default:
         layers.append((rng.uniform(-lim, lim, (fan_in, fan_out)).astype(np.float32), np.zeros(fan_out, dtype=np.float32)))
     networks.append(layers)
 bank = QNetworkBank(networks, seg, "cuda")
-eps = torch.full((P,), EPS_INIT, dtype=torch.float32, device=bank.device)
-bank.epsilon = eps
 learners = DQNLearnerBank(bank, gamma=gammas, tau=TAU, lr=lrs, strategy="double_ref", seed=args.seed)
 
 env = BatchedAqua(worlds, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()
 ring = DeviceReplayRing(env, capacity=args.rounds * worlds)   # a multiple of the batch: a slot belongs to one world
 tracker = EpisodeTracker(env)
-graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch).capture()
+segments = None
+if args.host_refresh:
+    eps = torch.full((P,), EPS_INIT, dtype=torch.float32, device=bank.device)
+else:
+    segments = SegmentTracker(tracker, seg, P, window=100, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))
+    eps = segments.epsilon
+bank.epsilon = eps
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
-episodes, seen = np.zeros(P, dtype=np.int64), 0               # finished episodes per network, and in all
+episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):
-    graph.launch()                                             # act, record, step, record, account, draw, update, tick
-    if step % args.refresh == 0:                               # host reads: the new records, then P floats back to the device
+    graph.launch()                                             # act, record, step, record, account, [segments,] draw, update, tick
+    if args.host_refresh and step % args.refresh == 0:         # host reads: the new records, then P floats back to the device
         total = tracker.counts()["episodes"]
         new = tracker.last(total - seen)                       # (at most the log's capacity of them)
         episodes += np.bincount(new["world"] // seg, minlength=P)[:P]
         seen = total
         eps.copy_(torch.from_numpy(np.maximum(EPS_FINAL, EPS_INIT * decay ** episodes).astype(np.float32)))
     if step % 100 == 0:
-        log = tracker.last(tracker.capacity)
-        owner = log["world"] // seg
         loss = learners.loss.cpu().numpy()
         print("step %6d  episodes %7d  ring %d" % (step, tracker.counts()["episodes"], ring.filled()))
+        if segments is not None:                               # P numbers each, as the device published them
+            done = [r["episodes"] for r in segments.counts()["segments"]]
+            last = [min(d, segments.window) for d in done]
+            reward, success = segments.mean_return.cpu().numpy(), segments.success_rate.cpu().numpy()
+        else:                                                  # the log read back and sorted out by owner on the host
+            log = tracker.last(tracker.capacity)
+            owner = log["world"] // seg
+            mine = [np.nonzero(owner == p)[0][-100:] for p in range(P)]
+            last = [m.size for m in mine]
+            reward = [float(log["ret"][m].sum()) / max(m.size, 1) for m in mine]
+            success = [float((log["code"][m] == 3).sum()) / max(m.size, 1) for m in mine]
+        now = eps.cpu().numpy()
         for p in range(P):
-            mine = np.nonzero(owner == p)[0][-100:]
-            k = max(mine.size, 1)
             print("    network %3d  lr %.2e  gamma %.3f  epsilon %.3f  last %3d episodes: reward %8.2f  success %3.0f %%  loss %10.4f" %
-                  (p, lrs[p], gammas[p], float(eps[p]), mine.size, float(log["ret"][mine].sum()) / k,
-                   100.0 * float((log["code"][mine] == 3).sum()) / k, float(loss[p])))
+                  (p, lrs[p], gammas[p], float(now[p]), last[p], float(reward[p]), 100.0 * float(success[p]), float(loss[p])))
 for p in range(P):
     learners.weights(p)                                        # bank.layers[p] now holds the trained network p
