@@ -128,6 +128,15 @@ class DQNLearnerBank(object):
         self.hyper[p].copy_(self.torch.from_numpy(packed[0]))
         return self
 
+    def sync_hyper(self):
+        """Read the device table back into the host copy behind hyper_of(), set_hyper() and state_dict() (a host read).
+        Only a PopulationSelector (pbt.py) rewrites rows of the device table: after its select() the host copy is stale
+        until this is called; its report() and state_dict() call it."""
+        if self.torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("sync_hyper() reads back to the host: call it outside of a graph capture")
+        self._hyper_host = self.hyper.cpu().numpy()[:, :len(_lbank_capi.HYPER_FIELDS)].copy()
+        return self
+
     # ------------------------------------------------------------------ the path
     def draw(self, ring, batch_size=64, out=None):
         """The minibatch of every network's NEXT update, each from its own slots of `ring` (a DeviceReplayRing whose

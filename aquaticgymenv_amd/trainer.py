@@ -178,14 +178,18 @@ class PopulationLoop(DQNLoop):
     With segments=, a SegmentTracker (segments.py) of this tracker whose epsilon array IS bank.epsilon, stage 5 is followed by
     its launch: every network's schedule advances by the episodes its worlds finished in this step (dqn.py:184), and its
     counters and windowed statistics follow, on the device.  Eleven kernels, and no host read is needed to keep the loop
-    correct.  There is no CPU path."""
+    correct.
 
-    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None):
+    With selector=, a PopulationSelector (pbt.py) of these learners and this SegmentTracker, its two launches follow the
+    SegmentTracker's and precede the draw: thirteen kernels.  A network replaced in an iteration is trained on its parent's
+    weights by the update of that same iteration.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
         of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
-        bank's segment size and number of networks, whose epsilon is bank.epsilon.  Everything on one device; anything else
-        is a ValueError."""
+        bank's segment size and number of networks, whose epsilon is bank.epsilon; selector: None, or a PopulationSelector
+        of `learners` and `segments`.  Everything on one device; anything else is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
@@ -217,11 +221,18 @@ class PopulationLoop(DQNLoop):
             if segments.seg != bank.seg or segments.segments != bank.networks:
                 raise ValueError("the SegmentTracker has %d segments of %d worlds, the bank %d networks of %d" %
                                  (segments.segments, segments.seg, bank.networks, bank.seg))
+        if selector is not None:
+            if not hasattr(selector, "select") or not hasattr(selector, "_warm_up"):
+                raise ValueError("expected a PopulationSelector")
+            if segments is None or selector.segments is not segments:
+                raise ValueError("the selector judges by another SegmentTracker than the loop's segments=")
+            if selector.learners is not learners:
+                raise ValueError("the selector selects among another learner bank than the one the loop trains")
         B = int(batch_size)
         if B < 1 or B > _lbank_capi.MAX_BATCH:
             raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _lbank_capi.MAX_BATCH))
         self.env, self.bank, self.learners, self.ring, self.tracker, self.batch_size = env, bank, learners, ring, tracker, B
-        self.segments = segments
+        self.segments, self.selector = segments, selector
         self.qnet = bank                                      # (what DQNLoop.capture() hands to the graph as its policy)
         self.torch = env.torch
         self.view = ring.learner_view()
@@ -247,6 +258,8 @@ class PopulationLoop(DQNLoop):
         self.tracker.after_step()
         if self.segments is not None:
             self.segments.account()
+        if self.selector is not None:
+            self.selector.select()
         self.learners.draw(ring, self.batch_size, out=self.idx)
         self.learners.update(self.view, self.batch_size, self.idx)
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
@@ -254,7 +267,8 @@ class PopulationLoop(DQNLoop):
     def _warm_up(self):
         """DQNLoop._warm_up's rule: every kernel of the iteration runs once, on the current stream, and leaves no trace.  The
         bank writes policy_action (an output); the accounting sees a batch in which no world counts; the ring kernels and the
-        bank draw run on a one-slot scratch ring; the SegmentTracker, if there is one, finds no new record; the learner bank
+        bank draw run on a one-slot scratch ring; the SegmentTracker, if there is one, finds no new record; the selector, if
+        there is one, runs on scratch state in which no network has finished an episode; the learner bank
         gets minibatches without a sample (documented to leave everything but loss and grad as it was, and those are put
         back); the step is taken on a snapshot and taken back."""
         from . import _lbank_capi
@@ -268,6 +282,8 @@ class PopulationLoop(DQNLoop):
                            torch.full((n,), -1, dtype=torch.int32, device=dev))
         if self.segments is not None:
             self.segments.account()                                          # no new record: its cursor is the log's already
+        if self.selector is not None:
+            self.selector._warm_up()                                         # scratch state, nobody scored: nothing is copied
         header = torch.zeros(rpl.HEADER_WORDS, dtype=torch.int64, device=dev)
         rows = torch.zeros((5, 1), dtype=torch.float32, device=dev)
         f32, u8 = torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.uint8, device=dev)

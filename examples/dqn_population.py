@@ -12,10 +12,17 @@ advances inside the graph: once per episode the network's worlds finish, as dqn.
 network's mean reward and success rate over its last 100 episodes (dqn.py:196-198) on the device.  Nothing is read back
 between two prints, and a print reads P numbers of each.
 
+--pbt selects among the networks while they train (population-based training, libaqua_pbt.so): every --pbt-every
+iterations the worst --pbt-fraction of the networks that have finished --pbt-ready episodes since their last replacement
+take the weights, the optimiser state and the perturbed lr and gamma of networks drawn from the best --pbt-fraction, inside
+the graph: thirteen kernels.  Each print then shows every slot's current lr and gamma, the initial network it descends from
+and the replacements so far.
+
 --host-refresh keeps the loop as it was before that library: ten kernels, eps refreshed from the host every --refresh
 iterations from the tracker's log, the statistics rebuilt on the host from the log.
 
     python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
+                                      [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1]
 """
 import argparse
 import os
@@ -43,8 +50,14 @@ ap.add_argument("--obstacles", action="store_true")
 ap.add_argument("--epsilon-decay", type=float, default=10000, help="episodes of a network to reach the final epsilon")
 ap.add_argument("--host-refresh", action="store_true", help="the schedule and the statistics on the host, as before the SegmentTracker")
 ap.add_argument("--refresh", type=int, default=50, help="with --host-refresh: iterations between two refreshes of the epsilon array")
+ap.add_argument("--pbt", action="store_true", help="select among the networks on the device (population-based training)")
+ap.add_argument("--pbt-ready", type=int, default=100, help="episodes a network finishes before it can be replaced (again)")
+ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the quantile that is replaced, and the one parents are drawn from")
+ap.add_argument("--pbt-every", type=int, default=1, help="iterations between two selections")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
+if args.pbt and args.host_refresh:
+    ap.error("--pbt judges the networks by the SegmentTracker's statistics: it does not go with --host-refresh")
 
 EPS_INIT, EPS_FINAL, TAU = 1.0, 0.05, 0.005                   # default_hyperparam of dqn.py
 P, seg = args.networks, args.seg
@@ -75,7 +88,12 @@ else:
     segments = SegmentTracker(tracker, seg, P, window=100, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))
     eps = segments.epsilon
 bank.epsilon = eps
-graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments).capture()
+selector = None
+if args.pbt:
+    from aquaticgymenv_amd.pbt import PopulationSelector
+    selector = PopulationSelector(learners, segments, score="mean_return", fraction=args.pbt_fraction, ready=args.pbt_ready,
+                                  every=args.pbt_every, seed=args.seed)
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
 episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):
@@ -101,6 +119,11 @@ for step in range(1, args.steps + 1):
             reward = [float(log["ret"][m].sum()) / max(m.size, 1) for m in mine]
             success = [float((log["code"][m] == 3).sum()) / max(m.size, 1) for m in mine]
         now = eps.cpu().numpy()
+        if selector is not None:                               # a host read: the counters, the lineage, and the table selection rewrites
+            report = selector.report()                         # (calls learners.sync_hyper(): hyper_of() is current again)
+            lrs, gammas = ([learners.hyper_of(p)[key] for p in range(P)] for key in ("lr", "gamma"))
+            print("    selections %d  replaced %d (%d by the last)  descend from %s" %
+                  (report["calls"], report["replaced"], report["last"], report["origin"].tolist()))
         for p in range(P):
             print("    network %3d  lr %.2e  gamma %.3f  epsilon %.3f  last %3d episodes: reward %8.2f  success %3.0f %%  loss %10.4f" %
                   (p, lrs[p], gammas[p], float(now[p]), last[p], float(reward[p]), 100.0 * float(success[p]), float(loss[p])))
