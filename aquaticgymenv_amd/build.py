@@ -85,9 +85,25 @@ SELECTION_LIBRARIES = {
 }
 
 
+def _source_library(name, headers):
+    """_library()'s entry with the header beside the source, at aquaticgymenv_amd/csrc/aqua_<name>.h"""
+    entry = _library(name, headers)
+    entry["deps"] = entry["deps"][:-1] + [os.path.join(HERE, "csrc", "aqua_%s.h" % name)]
+    return entry
+
+
+# Libraries behind those (the seven tables above and what ten_libraries() returns are pinned as well).
+# qmap: Q-value maps of every network of a bank, the reference's Q-value plotter on the device (csrc/aqua_qmap.h).  Its
+# header lies beside its source: the listings of both include/ directories are pinned (tests/test_segments_cpu.py,
+# tests/test_pbt_cpu.py).
+MAP_LIBRARIES = {
+    "qmap": _source_library("qmap", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the seven tables"""
-    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES):
+    """the table entry of library `name`, from any of the eight tables"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -121,6 +137,11 @@ def nine_libraries():
 def ten_libraries():
     """all ten libraries' names, the one of SELECTION_LIBRARIES included, in build order"""
     return nine_libraries() + list(SELECTION_LIBRARIES)
+
+
+def eleven_libraries():
+    """all eleven libraries' names, the one of MAP_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return ten_libraries() + list(MAP_LIBRARIES)
 
 
 def hipcc_path():
@@ -177,6 +198,8 @@ SEGMENTS_SRC, SEGMENTS_DEPS, SEGMENTS_LIB, SEGMENTS_FLAGS = (SEGMENT_LIBRARIES["
 build_segments, segments_needs_build = functools.partial(build_library, "segments"), functools.partial(needs_build, "segments")
 PBT_SRC, PBT_DEPS, PBT_LIB, PBT_FLAGS = (SELECTION_LIBRARIES["pbt"][k] for k in ("src", "deps", "lib", "flags"))
 build_pbt, pbt_needs_build = functools.partial(build_library, "pbt"), functools.partial(needs_build, "pbt")
+QMAP_SRC, QMAP_DEPS, QMAP_LIB, QMAP_FLAGS = (MAP_LIBRARIES["qmap"][k] for k in ("src", "deps", "lib", "flags"))
+build_qmap, qmap_needs_build = functools.partial(build_library, "qmap"), functools.partial(needs_build, "qmap")
 
 
 def build_variant(name, flags, verbose=False):
@@ -226,5 +249,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in nine_libraries() + list(SELECTION_LIBRARIES):
+    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))
