@@ -101,9 +101,18 @@ MAP_LIBRARIES = {
 }
 
 
+# Libraries behind those (the eight tables above and what eleven_libraries() returns are pinned as well).
+# fastpol: the fast acting path, the Q-network's hidden layers on the f16 MFMA with operands split hi / lo
+# (csrc/aqua_fastpol.h, beside its source as aqua_qmap.h is and for the same reason).
+FAST_LIBRARIES = {
+    "fastpol": _source_library("fastpol", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the eight tables"""
-    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES):
+    """the table entry of library `name`, from any of the nine tables"""
+    for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
+                  FAST_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -140,8 +149,13 @@ def ten_libraries():
 
 
 def eleven_libraries():
-    """all eleven libraries' names, the one of MAP_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    """all eleven libraries' names, the one of MAP_LIBRARIES included, in build order"""
     return ten_libraries() + list(MAP_LIBRARIES)
+
+
+def twelve_libraries():
+    """all twelve libraries' names, the one of FAST_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return eleven_libraries() + list(FAST_LIBRARIES)
 
 
 def hipcc_path():
@@ -200,6 +214,8 @@ PBT_SRC, PBT_DEPS, PBT_LIB, PBT_FLAGS = (SELECTION_LIBRARIES["pbt"][k] for k in 
 build_pbt, pbt_needs_build = functools.partial(build_library, "pbt"), functools.partial(needs_build, "pbt")
 QMAP_SRC, QMAP_DEPS, QMAP_LIB, QMAP_FLAGS = (MAP_LIBRARIES["qmap"][k] for k in ("src", "deps", "lib", "flags"))
 build_qmap, qmap_needs_build = functools.partial(build_library, "qmap"), functools.partial(needs_build, "qmap")
+FASTPOL_SRC, FASTPOL_DEPS, FASTPOL_LIB, FASTPOL_FLAGS = (FAST_LIBRARIES["fastpol"][k] for k in ("src", "deps", "lib", "flags"))
+build_fastpol, fastpol_needs_build = functools.partial(build_library, "fastpol"), functools.partial(needs_build, "fastpol")
 
 
 def build_variant(name, flags, verbose=False):
@@ -249,5 +265,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES):
+    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))

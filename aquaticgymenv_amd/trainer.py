@@ -13,7 +13,8 @@ DeviceReplayRing (replay.py) keeps them in device memory.  An iteration is then,
     5. ring close: (r, s', d), cursor and size move on
 
 step() queues exactly that eagerly; capture() records the same calls once and launch() replays them: eleven kernels, no
-host work between them.  Both give, bit for bit, what examples/dqn_train.py --eager computes with ReplayRing and
+host work between them.  With actor=, a FastActor (fastpolicy.py) over the acting network, stage 1 launches it and its
+refresh() follows stage 8: twelve kernels.  Both give, bit for bit, what examples/dqn_train.py --eager computes with ReplayRing and
 learner.update(ring, B).  There is no CPU path.
 """
 import ctypes
@@ -23,10 +24,12 @@ from .batched import RolloutGraph
 
 
 class DQNLoop(object):
-    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64):
+    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64, actor=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; qnet: the acting QNetwork; learner: the DQNLearner
-        that trains it; ring: a DeviceReplayRing of env; tracker: an EpisodeTracker of env with an epsilon schedule.
-        Everything on one device; anything else is a ValueError."""
+        that trains it; ring: a DeviceReplayRing of env; tracker: an EpisodeTracker of env with an epsilon schedule;
+        actor: None, or a FastActor (fastpolicy.py) over qnet -- the act stage then launches it, and one actor.refresh()
+        follows the update: one kernel more, eagerly and in the graph.  Everything on one device; anything else is a
+        ValueError."""
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
         if env.obs_norm_buf is None:
@@ -45,6 +48,7 @@ class DQNLoop(object):
         B = int(batch_size)
         if B < 1 or B > _learner_capi.MAX_BATCH:
             raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _learner_capi.MAX_BATCH))
+        self.actor = self._check_actor(actor, qnet)
         self.env, self.qnet, self.learner, self.ring, self.tracker, self.batch_size = env, qnet, learner, ring, tracker, B
         self.torch = env.torch
         self.view = ring.learner_view()
@@ -52,14 +56,33 @@ class DQNLoop(object):
         env.policy_action                                     # (allocated here, not inside a capture)
         learner._grow(B)
 
+    @staticmethod
+    def _check_actor(actor, policy):
+        """actor=: None, or a FastActor whose source is the loop's own network or bank"""
+        if actor is not None and (not hasattr(actor, "refresh") or getattr(actor, "source", None) is not policy):
+            raise ValueError("actor= must be a FastActor over the network (or bank) this loop trains")
+        return actor
+
+    def _act_fast(self, s):
+        """the act stage through the FastActor: its library's checker, its entry's name and its message"""
+        from . import _fastpol_capi
+        env = self.env
+        _fastpol_capi.check(env._policy_launch(self.actor, 0.0, 0, env._tick_dev.data_ptr(), s), "aquafast_act_f16")
+
+    def _act(self, s):
+        from . import _policy_capi
+        if self.actor is not None:
+            return self._act_fast(s)
+        env = self.env
+        _policy_capi.check(env._policy_launch(self.qnet, 0.0, 0, env._tick_dev.data_ptr(), s), "aquapol_act_f32")
+
     # ------------------------------------------------------------------ the iteration
     def _queue(self):
         """the nine stages on torch's current stream, every draw keyed by the device tick base"""
-        from . import _policy_capi
         env, ring, tracker = self.env, self.ring, self.tracker
         action, tb = env.policy_action, env._tick_dev
         s = env._stream()
-        _policy_capi.check(env._policy_launch(self.qnet, 0.0, 0, tb.data_ptr(), s), "aquapol_act_f32")
+        self._act(s)
         tracker.explore(action, tick=0, tick_base=tb)
         ring.before_step(action)
         _capi.check(env._step_launch(action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
@@ -68,6 +91,8 @@ class DQNLoop(object):
         tracker.after_step()
         ring.draw(self.batch_size, self.learner, out=self.idx)
         self.learner.update(self.view, self.batch_size, idx=self.idx)
+        if self.actor is not None:
+            self.actor.refresh()                              # the next iteration acts with the weights of this update
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
 
     def step(self):
@@ -87,13 +112,14 @@ class DQNLoop(object):
         scratch row; the accounting sees a batch in which no world counts; the ring kernels run on a one-slot scratch ring;
         the learner gets a minibatch without a sample (documented to leave everything as it was); the step is taken on a
         snapshot and taken back."""
-        from . import _policy_capi
         torch, env, tracker, learner = self.torch, self.env, self.tracker, self.learner
         dev, n = env.device, env.num_envs
         rpl = self.ring._capi
         s = env._stream()
         tb = env._tick_dev
-        _policy_capi.check(env._policy_launch(self.qnet, 0.0, 0, tb.data_ptr(), s), "aquapol_act_f32")
+        self._act(s)
+        if self.actor is not None:
+            self.actor.refresh()                              # (the weights have not changed: the same bytes again)
         tracker.explore(torch.zeros(env.ld, dtype=torch.uint8, device=dev), tick=0, tick_base=tb)
         tracker.after_step(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
                            torch.full((n,), -1, dtype=torch.int32, device=dev))
@@ -153,7 +179,7 @@ class DQNLoop(object):
             finally:
                 torch.cuda.current_stream(env.device).wait_stream(cap)
         g = RolloutGraph(env, handle, 1, env.reward, env.term)
-        g._actions = (self.qnet, env.policy_action)
+        g._actions = (self.actor or self.qnet, env.policy_action)
         g._loop = self                                        # the buffers the graph's nodes point at
         g.done_history = None
         return g
@@ -182,14 +208,19 @@ class PopulationLoop(DQNLoop):
 
     With selector=, a PopulationSelector (pbt.py) of these learners and this SegmentTracker, its two launches follow the
     SegmentTracker's and precede the draw: thirteen kernels.  A network replaced in an iteration is trained on its parent's
-    weights by the update of that same iteration.  There is no CPU path."""
+    weights by the update of that same iteration.
 
-    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None):
+    With actor=, a FastActor (fastpolicy.py) over the bank, stage 1 is its launch and its refresh() follows the bank update:
+    one kernel more in every variant above.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
         of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
         bank's segment size and number of networks, whose epsilon is bank.epsilon; selector: None, or a PopulationSelector
-        of `learners` and `segments`.  Everything on one device; anything else is a ValueError."""
+        of `learners` and `segments`; actor: None, or a FastActor (fastpolicy.py) over `bank` -- the act stage then launches it
+        and one actor.refresh() follows the bank update (which follows the selector when there is one): one kernel more.
+        Everything on one device; anything else is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
@@ -233,6 +264,7 @@ class PopulationLoop(DQNLoop):
             raise ValueError("batch_size=%d: must be in [1, %d]" % (B, _lbank_capi.MAX_BATCH))
         self.env, self.bank, self.learners, self.ring, self.tracker, self.batch_size = env, bank, learners, ring, tracker, B
         self.segments, self.selector = segments, selector
+        self.actor = self._check_actor(actor, bank)
         self.qnet = bank                                      # (what DQNLoop.capture() hands to the graph as its policy)
         self.torch = env.torch
         self.view = ring.learner_view()
@@ -242,6 +274,8 @@ class PopulationLoop(DQNLoop):
 
     def _act(self, s):
         from . import _bank_capi
+        if self.actor is not None:
+            return self._act_fast(s)
         env = self.env
         _bank_capi.check(env._policy_launch(self.bank, 0.0, 0, env._tick_dev.data_ptr(), s), "aquabank_act_f32")
 
@@ -262,6 +296,8 @@ class PopulationLoop(DQNLoop):
             self.selector.select()
         self.learners.draw(ring, self.batch_size, out=self.idx)
         self.learners.update(self.view, self.batch_size, self.idx)
+        if self.actor is not None:
+            self.actor.refresh()                              # every slot, behind the selector's copy and the update
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
 
     def _warm_up(self):
@@ -278,6 +314,8 @@ class PopulationLoop(DQNLoop):
         s = env._stream()
         tb = env._tick_dev
         self._act(s)
+        if self.actor is not None:
+            self.actor.refresh()                              # (the weights have not changed: the same bytes again)
         tracker.after_step(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
                            torch.full((n,), -1, dtype=torch.int32, device=dev))
         if self.segments is not None:

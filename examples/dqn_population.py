@@ -18,11 +18,14 @@ take the weights, the optimiser state and the perturbed lr and gamma of networks
 the graph: thirteen kernels.  Each print then shows every slot's current lr and gamma, the initial network it descends from
 and the replacements so far.
 
+--fast acts through FastActor(bank): the hidden layers of every network on the f16 MFMA with operands split hi / lo; one
+refresh of the split weights follows the update inside the graph, one kernel more.
+
 --host-refresh keeps the loop as it was before that library: ten kernels, eps refreshed from the host every --refresh
 iterations from the tracker's log, the statistics rebuilt on the host from the log.
 
     python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
-                                      [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1]
+                                      [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1] [--fast]
 """
 import argparse
 import os
@@ -54,6 +57,7 @@ ap.add_argument("--pbt", action="store_true", help="select among the networks on
 ap.add_argument("--pbt-ready", type=int, default=100, help="episodes a network finishes before it can be replaced (again)")
 ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the quantile that is replaced, and the one parents are drawn from")
 ap.add_argument("--pbt-every", type=int, default=1, help="iterations between two selections")
+ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor over the bank)")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 if args.pbt and args.host_refresh:
@@ -93,7 +97,11 @@ if args.pbt:
     from aquaticgymenv_amd.pbt import PopulationSelector
     selector = PopulationSelector(learners, segments, score="mean_return", fraction=args.pbt_fraction, ready=args.pbt_ready,
                                   every=args.pbt_every, seed=args.seed)
-graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector).capture()
+actor = None
+if args.fast:
+    from aquaticgymenv_amd.fastpolicy import FastActor
+    actor = FastActor(bank)
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
 episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):

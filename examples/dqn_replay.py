@@ -6,7 +6,10 @@ Policy.test / TestPlotter.run_tests of the reference evaluate a policy (aquaticg
 with restarts, recording the transitions into the device-side experience ring the way main/impl/dqn.py:174 appends them to
 its deque.
 
-    python examples/dqn_replay.py [--envs 16384] [--obstacles]
+--fast acts through FastActor (aquaticgymenv_amd.fastpolicy): the hidden layers on the f16 MFMA with operands split hi / lo,
+the same policy at float32-like accuracy in about 0.6 of the float32 kernel's time.
+
+    python examples/dqn_replay.py [--envs 16384] [--obstacles] [--fast]
 """
 import argparse
 import os
@@ -24,11 +27,15 @@ from aquaticgymenv_amd.qpolicy import QNetwork
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=16384)
 ap.add_argument("--obstacles", action="store_true", help="the policy trained with the default five obstacles")
+ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor)")
 args = ap.parse_args()
 
 z = np.load(os.path.join(ROOT, "tests", "golden", "dqn_policies.npz"))
 tag = "with_obs" if args.obstacles else "no_obs"
 qnet = QNetwork([(z["%s_kernel%d" % (tag, i)], z["%s_bias%d" % (tag, i)]) for i in range(3)], "cuda")
+if args.fast:
+    from aquaticgymenv_amd.fastpolicy import FastActor
+    qnet = FastActor(qnet)                                 # a policy wherever the QNetwork is one; its weights are fixed here
 
 # one episode per world, no restarts: the protocol of the published figures
 runs = BatchedAqua(args.envs, obstacles=args.obstacles, seed=2, auto_reset=False)

@@ -14,7 +14,10 @@ By default the whole iteration -- act, explore, record, step, record, account, d
 (trainer.DQNLoop over a DeviceReplayRing, whose cursor and size live on the device): one launch from Python per iteration
 instead of about sixteen.  --eager keeps the loop written out call by call with ReplayRing; both compute the same bits.
 
-    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager]
+--fast acts through a FastActor over the trained network (the hidden layers on the f16 MFMA, operands split hi / lo); its
+split copy of the weights is refreshed after every update, inside the graph: one kernel more.
+
+    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager] [--fast]
 """
 import argparse
 import os
@@ -42,6 +45,7 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--loss", choices=("mse", "reference"), default="mse",
                 help="mse: the mean squared TD error; reference: the broadcast loss main/impl/dqn.py:243-247 executes")
 ap.add_argument("--eager", action="store_true", help="issue every launch of the iteration from Python (ReplayRing) instead of replaying one graph")
+ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor, refreshed after every update)")
 args = ap.parse_args()
 
 # default_hyperparam of dqn.py
@@ -59,20 +63,26 @@ env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_rese
 env.reset()
 ring = (ReplayRing if args.eager else DeviceReplayRing)(env, capacity=max(args.buffer, args.envs))
 tracker = EpisodeTracker(env, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))     # decay >= 1: episodes to reach EPS_FINAL
-graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch).capture()
+actor = None
+if args.fast:
+    from aquaticgymenv_amd.fastpolicy import FastActor
+    actor = FastActor(qnet)
+graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch, actor=actor).capture()
 for step in range(1, args.steps + 1):
     if graph is not None:
         graph.launch()                                         # the nine stages below and the tick advance, as one graph
     else:
         # env.step(policy=qnet, epsilon=...) in three calls: greedy actions, the exploring draws under the device epsilon, and
         # the step, so that the ring sees the action before the step
-        action = qnet.act(env, epsilon=0.0, out=env.policy_action)
+        action = (actor or qnet).act(env, epsilon=0.0, out=env.policy_action)
         tracker.explore(env.policy_action)
         ring.before_step(env.policy_action)
         obs, reward, term = env.step(action)
         ring.after_step()
         tracker.after_step()                                   # returns, lengths, the log, epsilon: all on the device
         learner.update(ring, args.batch)                       # minibatch drawn on the device; qnet acts with the new weights
+        if actor is not None:
+            actor.refresh()                                    # ... and the fast actor after its re-split
     if step % 100 == 0:                                        # the only host reads of the loop
         c, last = tracker.counts(), tracker.last(100)
         k = max(len(last["ret"]), 1)
