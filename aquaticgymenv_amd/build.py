@@ -109,10 +109,18 @@ FAST_LIBRARIES = {
 }
 
 
+# Libraries behind those (the nine tables above and what twelve_libraries() returns are pinned as well).
+# nstep: multi-step returns, the n-step fold of the experience ring and the bootstrap discount of every network
+# (csrc/aqua_nstep.h, beside its source as aqua_qmap.h and aqua_fastpol.h are and for the same reason).
+NSTEP_LIBRARIES = {
+    "nstep": _source_library("nstep", ["aqua_host.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the nine tables"""
+    """the table entry of library `name`, from any of the ten tables"""
     for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
-                  FAST_LIBRARIES):
+                  FAST_LIBRARIES, NSTEP_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -156,6 +164,11 @@ def eleven_libraries():
 def twelve_libraries():
     """all twelve libraries' names, the one of FAST_LIBRARIES included, in build order (what build() and `python -m` compile)"""
     return eleven_libraries() + list(FAST_LIBRARIES)
+
+
+def thirteen_libraries():
+    """all thirteen libraries' names, the one of NSTEP_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return twelve_libraries() + list(NSTEP_LIBRARIES)
 
 
 def hipcc_path():
@@ -216,6 +229,8 @@ QMAP_SRC, QMAP_DEPS, QMAP_LIB, QMAP_FLAGS = (MAP_LIBRARIES["qmap"][k] for k in (
 build_qmap, qmap_needs_build = functools.partial(build_library, "qmap"), functools.partial(needs_build, "qmap")
 FASTPOL_SRC, FASTPOL_DEPS, FASTPOL_LIB, FASTPOL_FLAGS = (FAST_LIBRARIES["fastpol"][k] for k in ("src", "deps", "lib", "flags"))
 build_fastpol, fastpol_needs_build = functools.partial(build_library, "fastpol"), functools.partial(needs_build, "fastpol")
+NSTEP_SRC, NSTEP_DEPS, NSTEP_LIB, NSTEP_FLAGS = (NSTEP_LIBRARIES["nstep"][k] for k in ("src", "deps", "lib", "flags"))
+build_nstep, nstep_needs_build = functools.partial(build_library, "nstep"), functools.partial(needs_build, "nstep")
 
 
 def build_variant(name, flags, verbose=False):
@@ -265,5 +280,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES):
+    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))

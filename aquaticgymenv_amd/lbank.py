@@ -159,11 +159,13 @@ class DQNLearnerBank(object):
         _lbank_capi.check(rc, "aqualbank_draw")
         return out
 
-    def update(self, ring, batch_size, idx, idx_out=None):
+    def update(self, ring, batch_size, idx, idx_out=None, hyper=None):
         """One update of every network from `ring` (ring.learner_view(), or anything with the s, a, r, s2, d, ok tensors,
         capacity and size of a ring of discrete actions), queued on torch's current stream.  idx: int32 [P][batch_size],
         row p the slots of network p's minibatch (draw()); a slot outside [0, ring.size) or with ok == 0 is not a sample.
-        idx_out: optional int32 [P][batch_size] receiving the slots used.  Two launches.  -> self.loss [P] (the loss of every
+        idx_out: optional int32 [P][batch_size] receiving the slots used.  hyper: None, or the device table of THIS call in place of
+        self.hyper, a float64 tensor of its shape -- NStepReturns.hyper (nstep.py), the table with gamma^n in word 0, with that
+        object's staged rows.  Two launches.  -> self.loss [P] (the loss of every
         network before the update; the gradients are left in self.grad)"""
         torch = self.torch
         if ring.a.dtype != torch.uint8 or ring.a.dim() != 1:
@@ -180,13 +182,18 @@ class DQNLearnerBank(object):
         self._idx(idx, B, "idx")
         if idx_out is not None:
             self._idx(idx_out, B, "idx_out")
+        if hyper is None:
+            hyper = self.hyper
+        elif not isinstance(hyper, torch.Tensor) or hyper.dtype != self.hyper.dtype or hyper.device != self.device \
+                or hyper.shape != self.hyper.shape or not hyper.is_contiguous():
+            raise ValueError("hyper must be a contiguous %s %s tensor on %s" % (self.hyper.dtype, tuple(self.hyper.shape), self.device))
         need = self._grow(B)
         with torch.cuda.device(self.device):
             rc = _lbank_capi.lib.aqualbank_update_f32(
                 self.theta.data_ptr(), self.theta_target.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.t.data_ptr(), self.networks,
                 ring.s.data_ptr(), ring.a.data_ptr(), ring.r.data_ptr(), ring.s2.data_ptr(), ring.d.data_ptr(), ring.ok.data_ptr(),
                 cap, int(ring.size), idx.data_ptr(), B,
-                _learner_capi.STRATEGIES[self.strategy] | _learner_capi.LOSSES[self.loss_form], self.hyper.data_ptr(),
+                _learner_capi.STRATEGIES[self.strategy] | _learner_capi.LOSSES[self.loss_form], hyper.data_ptr(),
                 self.bank.tensor.data_ptr(), self.target_tensor.data_ptr(), self.perm.data_ptr(), self.blob_floats,
                 self._workspace.data_ptr(), need,
                 None if idx_out is None else idx_out.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), self._stream())

@@ -76,13 +76,14 @@ class DQNLearner(object):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ the path
-    def update(self, ring, batch_size=64, idx=None, idx_out=None):
+    def update(self, ring, batch_size=64, idx=None, idx_out=None, gamma=None):
         """One update from `ring` (a ReplayRing of discrete actions, or anything with its s, a, r, s2, d, ok tensors,
         capacity and size), queued on torch's current stream of the ring's device.
-        idx: int32 [batch_size] slots; None: drawn on the device (Philox stream 6, keyed by seed, the sample number and the
+        idx: int32 [batch_size] (or [1][batch_size], one network's row of a bank's draw) slots; None: drawn on the device (Philox stream 6, keyed by seed, the sample number and the
         update number).  A slot outside [0, ring.size) or with ok == 0 is not a sample.  idx_out: optional int32
         [batch_size] receiving the slot used (-1: none).  The loss before the update is left in self.loss, the gradient in
-        self.grad.  -> self.loss"""
+        self.grad.  gamma: None, or the discount of THIS call in place of self.gamma -- gamma^n with the staged rows of an
+        NStepReturns (nstep.py), whose idx is int32 [1][batch_size].  -> self.loss"""
         torch = self.torch
         if ring.a.dtype != torch.uint8 or ring.a.dim() != 1:
             raise ValueError("the Q-network (main/impl/dqn.py) is defined for discrete actions: the ring holds continuous ones")
@@ -97,8 +98,10 @@ class DQNLearner(object):
                 raise ValueError("ring.%s must be a contiguous %s tensor of %d x %d" % (name, dtype, rows, cap))
         for name, t in (("idx", idx), ("idx_out", idx_out)):
             if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device
-                                  or t.dim() != 1 or t.numel() < B or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous int32 [>=%d] tensor on %s" % (name, B, self.device))
+                                  or not (t.dim() == 1 or (name == "idx" and t.dim() == 2 and t.shape[0] == 1))
+                                  or t.numel() < B or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous int32 [>=%d]%s tensor on %s"
+                                 % (name, B, " or [1][>=%d]" % B if name == "idx" else "", self.device))
         need = self._grow(B)
         with torch.cuda.device(self.device):
             rc = _learner_capi.lib.aqualrn_update_f32(
@@ -106,7 +109,7 @@ class DQNLearner(object):
                 ring.s.data_ptr(), ring.a.data_ptr(), ring.r.data_ptr(), ring.s2.data_ptr(), ring.d.data_ptr(),
                 ring.ok.data_ptr(), cap, int(ring.size),
                 None if idx is None else idx.data_ptr(), B, self.seed,
-                _learner_capi.STRATEGIES[self.strategy] | _learner_capi.LOSSES[self.loss_form], self.gamma, self.tau, self.lr, self.beta1, self.beta2, self.eps,
+                _learner_capi.STRATEGIES[self.strategy] | _learner_capi.LOSSES[self.loss_form], self.gamma if gamma is None else float(gamma), self.tau, self.lr, self.beta1, self.beta2, self.eps,
                 self.qnet.blob.data_ptr(), self.target_blob.data_ptr(), self.perm.data_ptr(), self.qnet.blob.numel() // 4,
                 self._workspace.data_ptr(), need,
                 None if idx_out is None else idx_out.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), self._stream())

@@ -15,7 +15,9 @@ DeviceReplayRing (replay.py) keeps them in device memory.  An iteration is then,
 step() queues exactly that eagerly; capture() records the same calls once and launch() replays them: eleven kernels, no
 host work between them.  With actor=, a FastActor (fastpolicy.py) over the acting network, stage 1 launches it and its
 refresh() follows stage 8: twelve kernels.  Both give, bit for bit, what examples/dqn_train.py --eager computes with ReplayRing and
-learner.update(ring, B).  There is no CPU path.
+learner.update(ring, B).  With n_step > 1, an NStepReturns (nstep.py) folds the draw between stages 7 and 8 -- one kernel more in
+either variant, twelve or thirteen -- and the update learns the n-step target from its staged rows with the discount
+gamma^n; n_step = 1 is the chain above, node for node.  There is no CPU path.
 """
 import ctypes
 
@@ -24,12 +26,14 @@ from .batched import RolloutGraph
 
 
 class DQNLoop(object):
-    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64, actor=None):
+    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64, actor=None, n_step=1):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; qnet: the acting QNetwork; learner: the DQNLearner
         that trains it; ring: a DeviceReplayRing of env; tracker: an EpisodeTracker of env with an epsilon schedule;
         actor: None, or a FastActor (fastpolicy.py) over qnet -- the act stage then launches it, and one actor.refresh()
-        follows the update: one kernel more, eagerly and in the graph.  Everything on one device; anything else is a
-        ValueError."""
+        follows the update: one kernel more, eagerly and in the graph.  n_step: 1, or the window of an n-step target
+        (nstep.py): one fold launch then goes between the draw and the update, and the ring's capacity must be a multiple of
+        env.num_envs.  The discount gamma^n is passed to the update by value: a graph keeps the one of its capture.
+        Everything on one device; anything else is a ValueError."""
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
         if env.obs_norm_buf is None:
@@ -53,8 +57,17 @@ class DQNLoop(object):
         self.torch = env.torch
         self.view = ring.learner_view()
         self.idx = self.torch.full((B,), -1, dtype=self.torch.int32, device=env.device)
+        self.nstep = self._make_nstep(ring, n_step, B, 1)
         env.policy_action                                     # (allocated here, not inside a capture)
         learner._grow(B)
+
+    def _make_nstep(self, ring, n_step, B, networks):
+        """n_step == 1: None, nothing is built; otherwise the NStepReturns of this loop"""
+        self.n_step = int(n_step)
+        if self.n_step == 1:
+            return None
+        from .nstep import NStepReturns
+        return NStepReturns(ring, self.n_step, B, networks=networks)
 
     @staticmethod
     def _check_actor(actor, policy):
@@ -90,7 +103,12 @@ class DQNLoop(object):
         ring.after_step()
         tracker.after_step()
         ring.draw(self.batch_size, self.learner, out=self.idx)
-        self.learner.update(self.view, self.batch_size, idx=self.idx)
+        if self.nstep is None:
+            self.learner.update(self.view, self.batch_size, idx=self.idx)
+        else:
+            nstep, gamma = self.nstep, self.learner.gamma
+            nstep.fold(self.idx, gamma=gamma)
+            self.learner.update(nstep.view, self.batch_size, idx=nstep.idx, gamma=nstep.discount(gamma))
         if self.actor is not None:
             self.actor.refresh()                              # the next iteration acts with the weights of this update
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
@@ -110,8 +128,8 @@ class DQNLoop(object):
         """Every kernel of the iteration runs once, on the current stream, and leaves no trace: the kernels' code is on the
         device before the capture begins.  The policy writes policy_action (an output); the exploration pass works on a
         scratch row; the accounting sees a batch in which no world counts; the ring kernels run on a one-slot scratch ring;
-        the learner gets a minibatch without a sample (documented to leave everything as it was); the step is taken on a
-        snapshot and taken back."""
+        the learner gets a minibatch without a sample (documented to leave everything as it was); the fold, if there is
+        one, runs on scratch rows with a draw without a sample; the step is taken on a snapshot and taken back."""
         torch, env, tracker, learner = self.torch, self.env, self.tracker, self.learner
         dev, n = env.device, env.num_envs
         rpl = self.ring._capi
@@ -134,6 +152,8 @@ class DQNLoop(object):
         rpl.check(rpl.lib.aquarpl_draw(header.data_ptr(), u8[1:].data_ptr(), 1, learner.t.data_ptr(), learner.seed, idx.data_ptr(),
                                        self.batch_size, s), "aquarpl_draw")
         idx.fill_(-1)
+        if self.nstep is not None:
+            self.nstep._warm_up(with_table=False)
         loss = learner.loss.clone()
         grad = learner.grad.clone()
         learner.update(self.view, self.batch_size, idx=idx)                  # no sample: nothing but loss and grad is written
@@ -148,7 +168,7 @@ class DQNLoop(object):
 
     def capture(self):
         """-> a RolloutGraph whose launch() replays one iteration: the nine stages as ONE chain of eleven kernel nodes (no
-        parallel branches).  It reads and advances the device state only -- tick base, epsilon, ring header, Adam's t -- so
+        parallel branches; one node more with an actor, one more with n_step > 1).  It reads and advances the device state only -- tick base, epsilon, ring header, Adam's t -- so
         every replay acts, explores, appends, draws and learns afresh; qnet.load() or learner.load_state_dict() between
         replays takes effect on the next one.  The learner's workspace is grown and every kernel has run before the capture."""
         torch, env, lib = self.torch, self.env, _capi.lib
@@ -211,15 +231,21 @@ class PopulationLoop(DQNLoop):
     weights by the update of that same iteration.
 
     With actor=, a FastActor (fastpolicy.py) over the bank, stage 1 is its launch and its refresh() follows the bank update:
-    one kernel more in every variant above.  There is no CPU path."""
+    one kernel more in every variant above.
 
-    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None):
+    With n_step > 1, an NStepReturns (nstep.py) folds the draw between stages 6 and 7: one kernel more in every variant above.
+    It reads learners.hyper and writes its own table with gamma_p^n in word 0, which the bank update of the same iteration
+    reads: after the selector has perturbed a gamma, that iteration already bootstraps with the new gamma^n, and no host read
+    is involved.  n_step = 1 is the chain above, node for node.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None, n_step=1):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
         of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
         bank's segment size and number of networks, whose epsilon is bank.epsilon; selector: None, or a PopulationSelector
         of `learners` and `segments`; actor: None, or a FastActor (fastpolicy.py) over `bank` -- the act stage then launches it
         and one actor.refresh() follows the bank update (which follows the selector when there is one): one kernel more.
+        n_step: 1, or the window of an n-step target (nstep.py): one fold launch between the draw and the update.
         Everything on one device; anything else is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
@@ -269,6 +295,7 @@ class PopulationLoop(DQNLoop):
         self.torch = env.torch
         self.view = ring.learner_view()
         self.idx = self.torch.full((bank.networks, B), -1, dtype=self.torch.int32, device=env.device)
+        self.nstep = self._make_nstep(ring, n_step, B, bank.networks)
         env.policy_action                                     # (allocated here, not inside a capture)
         learners._grow(B)
 
@@ -295,7 +322,12 @@ class PopulationLoop(DQNLoop):
         if self.selector is not None:
             self.selector.select()
         self.learners.draw(ring, self.batch_size, out=self.idx)
-        self.learners.update(self.view, self.batch_size, self.idx)
+        if self.nstep is None:
+            self.learners.update(self.view, self.batch_size, self.idx)
+        else:
+            nstep = self.nstep
+            nstep.fold(self.idx, hyper=self.learners.hyper)   # the table as the selector left it -> gamma^n, on the device
+            self.learners.update(nstep.view, self.batch_size, nstep.idx, hyper=nstep.hyper)
         if self.actor is not None:
             self.actor.refresh()                              # every slot, behind the selector's copy and the update
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
@@ -306,7 +338,8 @@ class PopulationLoop(DQNLoop):
         bank draw run on a one-slot scratch ring; the SegmentTracker, if there is one, finds no new record; the selector, if
         there is one, runs on scratch state in which no network has finished an episode; the learner bank
         gets minibatches without a sample (documented to leave everything but loss and grad as it was, and those are put
-        back); the step is taken on a snapshot and taken back."""
+        back); the fold, if there is one, runs on scratch rows and a scratch table with a draw without a sample; the step is
+        taken on a snapshot and taken back."""
         from . import _lbank_capi
         torch, env, tracker, learners = self.torch, self.env, self.tracker, self.learners
         dev, n = env.device, env.num_envs
@@ -334,6 +367,8 @@ class PopulationLoop(DQNLoop):
                                                          learners.t.data_ptr(), learners.seed_dev.data_ptr(), idx.data_ptr(),
                                                          self.batch_size, s), "aqualbank_draw")
         idx.fill_(-1)
+        if self.nstep is not None:
+            self.nstep._warm_up(with_table=True)
         loss = learners.loss.clone()
         grad = learners.grad.clone()
         learners.update(self.view, self.batch_size, idx)                     # no sample: nothing but loss and grad is written

@@ -24,8 +24,11 @@ refresh of the split weights follows the update inside the graph, one kernel mor
 --host-refresh keeps the loop as it was before that library: ten kernels, eps refreshed from the host every --refresh
 iterations from the tracker's log, the statistics rebuilt on the host from the log.
 
+--n-step K learns the K-step target: one more kernel folds the draw (nstep.NStepReturns) and derives every network's
+gamma^K from the learners' device table, so a gamma --pbt has just perturbed is the one the same iteration bootstraps with.
+
     python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
-                                      [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1] [--fast]
+                                      [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1] [--fast] [--n-step 3]
 """
 import argparse
 import os
@@ -59,6 +62,7 @@ ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the quantile t
 ap.add_argument("--pbt-every", type=int, default=1, help="iterations between two selections")
 ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor over the bank)")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--n-step", type=int, default=1, help="the window of the multi-step target (1: the reference's one-step target)")
 args = ap.parse_args()
 if args.pbt and args.host_refresh:
     ap.error("--pbt judges the networks by the SegmentTracker's statistics: it does not go with --host-refresh")
@@ -101,7 +105,7 @@ actor = None
 if args.fast:
     from aquaticgymenv_amd.fastpolicy import FastActor
     actor = FastActor(bank)
-graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor).capture()
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor, n_step=args.n_step).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
 episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):

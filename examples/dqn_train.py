@@ -17,7 +17,10 @@ instead of about sixteen.  --eager keeps the loop written out call by call with 
 --fast acts through a FastActor over the trained network (the hidden layers on the f16 MFMA, operands split hi / lo); its
 split copy of the weights is refreshed after every update, inside the graph: one kernel more.
 
-    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager] [--fast]
+--n-step K learns the K-step target: one more kernel in the graph folds the K transitions that follow every drawn one into a
+staged minibatch (nstep.NStepReturns), and the update bootstraps with gamma^K.  The ring then holds whole batched steps.
+
+    python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager] [--fast] [--n-step 3]
 """
 import argparse
 import os
@@ -46,7 +49,10 @@ ap.add_argument("--loss", choices=("mse", "reference"), default="mse",
                 help="mse: the mean squared TD error; reference: the broadcast loss main/impl/dqn.py:243-247 executes")
 ap.add_argument("--eager", action="store_true", help="issue every launch of the iteration from Python (ReplayRing) instead of replaying one graph")
 ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor, refreshed after every update)")
+ap.add_argument("--n-step", type=int, default=1, help="the window of the multi-step target (1: the reference's one-step target)")
 args = ap.parse_args()
+if args.n_step != 1 and args.eager:
+    ap.error("--n-step folds the device ring: it goes with the graph, not with --eager")
 
 # default_hyperparam of dqn.py
 EPS_INIT, EPS_FINAL, GAMMA, TAU = 1.0, 0.05, 0.98, 0.005
@@ -61,13 +67,16 @@ learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref",
 
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()
-ring = (ReplayRing if args.eager else DeviceReplayRing)(env, capacity=max(args.buffer, args.envs))
+capacity = max(args.buffer, args.envs)
+if args.n_step != 1:
+    capacity -= capacity % args.envs                           # whole batched steps: a world's next step is one batch further
+ring = (ReplayRing if args.eager else DeviceReplayRing)(env, capacity=capacity)
 tracker = EpisodeTracker(env, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))     # decay >= 1: episodes to reach EPS_FINAL
 actor = None
 if args.fast:
     from aquaticgymenv_amd.fastpolicy import FastActor
     actor = FastActor(qnet)
-graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch, actor=actor).capture()
+graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch, actor=actor, n_step=args.n_step).capture()
 for step in range(1, args.steps + 1):
     if graph is not None:
         graph.launch()                                         # the nine stages below and the tick advance, as one graph
