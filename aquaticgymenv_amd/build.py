@@ -117,10 +117,18 @@ NSTEP_LIBRARIES = {
 }
 
 
+# Libraries behind those (the ten tables above and what thirteen_libraries() returns are pinned as well).
+# prio: prioritised experience replay, a sum tree per network over the ring and the bank update with importance weights
+# (csrc/aqua_prio.h, beside its source for the same reason); its update kernels are the learner's, stated once in aqua_lrn.hpp.
+PRIORITY_LIBRARIES = {
+    "prio": _source_library("prio", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp", "aqua_lrn.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the ten tables"""
+    """the table entry of library `name`, from any of the eleven tables"""
     for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
-                  FAST_LIBRARIES, NSTEP_LIBRARIES):
+                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -169,6 +177,11 @@ def twelve_libraries():
 def thirteen_libraries():
     """all thirteen libraries' names, the one of NSTEP_LIBRARIES included, in build order (what build() and `python -m` compile)"""
     return twelve_libraries() + list(NSTEP_LIBRARIES)
+
+
+def fourteen_libraries():
+    """all fourteen libraries' names, the one of PRIORITY_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return thirteen_libraries() + list(PRIORITY_LIBRARIES)
 
 
 def hipcc_path():
@@ -231,6 +244,8 @@ FASTPOL_SRC, FASTPOL_DEPS, FASTPOL_LIB, FASTPOL_FLAGS = (FAST_LIBRARIES["fastpol
 build_fastpol, fastpol_needs_build = functools.partial(build_library, "fastpol"), functools.partial(needs_build, "fastpol")
 NSTEP_SRC, NSTEP_DEPS, NSTEP_LIB, NSTEP_FLAGS = (NSTEP_LIBRARIES["nstep"][k] for k in ("src", "deps", "lib", "flags"))
 build_nstep, nstep_needs_build = functools.partial(build_library, "nstep"), functools.partial(needs_build, "nstep")
+PRIO_SRC, PRIO_DEPS, PRIO_LIB, PRIO_FLAGS = (PRIORITY_LIBRARIES["prio"][k] for k in ("src", "deps", "lib", "flags"))
+build_prio, prio_needs_build = functools.partial(build_library, "prio"), functools.partial(needs_build, "prio")
 
 
 def build_variant(name, flags, verbose=False):
@@ -280,5 +295,5 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES):
+    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES) + list(PRIORITY_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))

@@ -90,6 +90,9 @@ struct GradArgs {
     uint64_t* ws_t;
     float* ws;
     int32_t* idx_out;
+    // read and written by grad_body<STRAT, true> alone (libaqua_prio.so); the LAST fields: no other kernel loads them
+    const float* weight = nullptr;           // [B] importance weights of the samples
+    float* td_out = nullptr;                 // [B] |Q(s)[a] - y| of every sample, -1 for what is no sample
 };
 
 // One forward pass of the network with parameters P for the 32 samples of a tile.  x[s]: input 2 s + h of the lane's
@@ -170,8 +173,9 @@ __device__ __forceinline__ int argmax3(const double (&q)[ACT])    // np.argmax: 
 __device__ __forceinline__ double pick3(const double (&q)[ACT], int a) { return a == 0 ? q[0] : (a == 1 ? q[1] : q[2]); }
 
 // The gradient kernel's body for workgroup `block` of a launch of BLOCK threads: the partial sums of its tiles into
-// a.ws + block * WS_STRIDE.  Everything in `a` is wavefront-uniform.
-template <int STRAT>
+// a.ws + block * WS_STRIDE.  Everything in `a` is wavefront-uniform.  WEIGHTED: the importance weights of prioritised
+// replay multiply the TD error's derivative and its square, and the plain TD error is written out (csrc/aqua_prio.h).
+template <int STRAT, bool WEIGHTED = false>
 __device__ __forceinline__ void grad_body(const GradArgs& a, const unsigned block)
 {
 #pragma clang fp contract(off)
@@ -293,6 +297,13 @@ __device__ __forceinline__ void grad_body(const GradArgs& a, const unsigned bloc
             const double e1 = qa - qo1, e2 = qa - qo2;
             delta64 = valid ? 3.0 * qa - y - qo1 - qo2 : 0.0;
             sq = valid ? sq + e1 * e1 + e2 * e2 : 0.0;
+        }
+        if constexpr (WEIGHTED) {
+            // (valid implies j < a.B; a weight of exactly 1 leaves both products the bits they had)
+            const double w = valid ? static_cast<double>(a.weight[j]) : 0.0;
+            if (h == 0 && j < a.B) a.td_out[j] = valid ? static_cast<float>(fabs(qa - y)) : -1.0f;
+            delta64 = w * delta64;
+            sq = w * sq;
         }
         const float delta = static_cast<float>(delta64);     // the one rounding between h2 and the backward pass
         loss += sq;

@@ -236,9 +236,16 @@ class PopulationLoop(DQNLoop):
     With n_step > 1, an NStepReturns (nstep.py) folds the draw between stages 6 and 7: one kernel more in every variant above.
     It reads learners.hyper and writes its own table with gamma_p^n in word 0, which the bank update of the same iteration
     reads: after the selector has perturbed a gamma, that iteration already bootstraps with the new gamma^n, and no host read
-    is involved.  n_step = 1 is the chain above, node for node.  There is no CPU path."""
+    is involved.  n_step = 1 is the chain above, node for node.
 
-    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None, n_step=1):
+    With priorities=, a PrioritizedReplay (priority.py) of this ring and these learners, replay is prioritised: its insert()
+    follows stage 4, its draw() (two launches) is stage 6, its update() (two launches) is stage 7 and its set() follows it --
+    three kernels more in every variant above.  With n_step > 1 the fold takes the draw's slots, the update the staged rows, and
+    set() the draw's slots again; a window the fold dropped keeps its priority.  priorities=None is the chain above, node for
+    node.  There is no CPU path."""
+
+    def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None, n_step=1,
+                 priorities=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
         of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
@@ -246,6 +253,7 @@ class PopulationLoop(DQNLoop):
         of `learners` and `segments`; actor: None, or a FastActor (fastpolicy.py) over `bank` -- the act stage then launches it
         and one actor.refresh() follows the bank update (which follows the selector when there is one): one kernel more.
         n_step: 1, or the window of an n-step target (nstep.py): one fold launch between the draw and the update.
+        priorities: None, or a PrioritizedReplay (priority.py) of `ring` and `learners`: three kernels more.
         Everything on one device; anything else is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
@@ -296,6 +304,14 @@ class PopulationLoop(DQNLoop):
         self.view = ring.learner_view()
         self.idx = self.torch.full((bank.networks, B), -1, dtype=self.torch.int32, device=env.device)
         self.nstep = self._make_nstep(ring, n_step, B, bank.networks)
+        if priorities is not None:
+            if not hasattr(priorities, "insert") or not hasattr(priorities, "_warm_up"):
+                raise ValueError("expected a PrioritizedReplay")
+            if priorities.ring is not ring or priorities.learners is not learners:
+                raise ValueError("the PrioritizedReplay keeps the priorities of another ring or another learner bank")
+            priorities._grow(B)
+            self.idx = priorities.idx                         # the draw's own row: what set() names
+        self.priorities = priorities
         env.policy_action                                     # (allocated here, not inside a capture)
         learners._grow(B)
 
@@ -316,18 +332,25 @@ class PopulationLoop(DQNLoop):
         _capi.check(env._step_launch(action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
                                      env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")
         ring.after_step()
+        per = self.priorities
+        if per is not None:
+            per.insert()                                      # the batch just closed, with the largest priority so far
         self.tracker.after_step()
         if self.segments is not None:
             self.segments.account()
         if self.selector is not None:
             self.selector.select()
-        self.learners.draw(ring, self.batch_size, out=self.idx)
+        # the uniform draw and the bank's update, or the descent of the sum trees and the update with its weights
+        draw = self.learners.draw(ring, self.batch_size, out=self.idx) if per is None else per.draw(self.batch_size, out=self.idx)
+        update = self.learners.update if per is None else per.update
         if self.nstep is None:
-            self.learners.update(self.view, self.batch_size, self.idx)
+            update(self.view, self.batch_size, draw)
         else:
             nstep = self.nstep
-            nstep.fold(self.idx, hyper=self.learners.hyper)   # the table as the selector left it -> gamma^n, on the device
-            self.learners.update(nstep.view, self.batch_size, nstep.idx, hyper=nstep.hyper)
+            nstep.fold(draw, hyper=self.learners.hyper)       # the table as the selector left it -> gamma^n, on the device
+            update(nstep.view, self.batch_size, nstep.idx, hyper=nstep.hyper)
+        if per is not None:
+            per.set(draw)                                     # the slots of the draw, not the staged positions
         if self.actor is not None:
             self.actor.refresh()                              # every slot, behind the selector's copy and the update
         _capi.check(_capi.lib.aqua_tick_advance(tb.data_ptr(), 1, s), "aqua_tick_advance")
@@ -338,7 +361,8 @@ class PopulationLoop(DQNLoop):
         bank draw run on a one-slot scratch ring; the SegmentTracker, if there is one, finds no new record; the selector, if
         there is one, runs on scratch state in which no network has finished an episode; the learner bank
         gets minibatches without a sample (documented to leave everything but loss and grad as it was, and those are put
-        back); the fold, if there is one, runs on scratch rows and a scratch table with a draw without a sample; the step is
+        back); the fold, if there is one, runs on scratch rows and a scratch table with a draw without a sample; a
+        PrioritizedReplay, if there is one, runs on a scratch tree and its update takes the learner bank's place; the step is
         taken on a snapshot and taken back."""
         from . import _lbank_capi
         torch, env, tracker, learners = self.torch, self.env, self.tracker, self.learners
@@ -369,11 +393,14 @@ class PopulationLoop(DQNLoop):
         idx.fill_(-1)
         if self.nstep is not None:
             self.nstep._warm_up(with_table=True)
-        loss = learners.loss.clone()
-        grad = learners.grad.clone()
-        learners.update(self.view, self.batch_size, idx)                     # no sample: nothing but loss and grad is written
-        learners.loss.copy_(loss)
-        learners.grad.copy_(grad)
+        if self.priorities is not None:
+            self.priorities._warm_up(self.view)                              # scratch trees; its update, without a sample
+        else:
+            loss = learners.loss.clone()
+            grad = learners.grad.clone()
+            learners.update(self.view, self.batch_size, idx)                 # no sample: nothing but loss and grad is written
+            learners.loss.copy_(loss)
+            learners.grad.copy_(grad)
         snap = env.snapshot()
         _capi.check(env._step_launch(env.policy_action.data_ptr(), _capi.ACT_U8, 0, 0, tb.data_ptr(), env.reward.data_ptr(),
                                      env.term.data_ptr(), env.done_bits.data_ptr(), s), "aqua_step_f32")

@@ -27,8 +27,14 @@ iterations from the tracker's log, the statistics rebuilt on the host from the l
 --n-step K learns the K-step target: one more kernel folds the draw (nstep.NStepReturns) and derives every network's
 gamma^K from the learners' device table, so a gamma --pbt has just perturbed is the one the same iteration bootstraps with.
 
+--per replaces the uniform draw by prioritised replay (priority.PrioritizedReplay, libaqua_prio.so): a sum tree per network
+over its slots of the ring, importance weights in the update, the new TD errors back into the tree -- three more kernels, all
+inside the graph.  --per-alpha, --per-beta0 and --per-anneal are the exponent of the priorities, the first importance exponent
+and the updates over which it rises to 1.
+
     python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
                                       [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1] [--fast] [--n-step 3]
+                                      [--per] [--per-alpha 0.6] [--per-beta0 0.4] [--per-anneal 100000]
 """
 import argparse
 import os
@@ -63,6 +69,10 @@ ap.add_argument("--pbt-every", type=int, default=1, help="iterations between two
 ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor over the bank)")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--n-step", type=int, default=1, help="the window of the multi-step target (1: the reference's one-step target)")
+ap.add_argument("--per", action="store_true", help="prioritised experience replay on the device (PrioritizedReplay)")
+ap.add_argument("--per-alpha", type=float, default=0.6, help="with --per: the exponent of the priorities (0: uniform)")
+ap.add_argument("--per-beta0", type=float, default=0.4, help="with --per: the importance exponent of the first update")
+ap.add_argument("--per-anneal", type=int, default=100000, help="with --per: updates over which the importance exponent rises to 1")
 args = ap.parse_args()
 if args.pbt and args.host_refresh:
     ap.error("--pbt judges the networks by the SegmentTracker's statistics: it does not go with --host-refresh")
@@ -105,7 +115,12 @@ actor = None
 if args.fast:
     from aquaticgymenv_amd.fastpolicy import FastActor
     actor = FastActor(bank)
-graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor, n_step=args.n_step).capture()
+priorities = None
+if args.per:
+    from aquaticgymenv_amd.priority import PrioritizedReplay
+    priorities = PrioritizedReplay(ring, learners, alpha=args.per_alpha, beta0=args.per_beta0, anneal=args.per_anneal)
+graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor, n_step=args.n_step,
+                       priorities=priorities).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
 episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):

@@ -1,0 +1,200 @@
+"""A numpy / Python-integer model of aquaticgymenv_amd/csrc/aqua_prio.h for tests/test_prio_*.py: the layout of the trees,
+the integer tree itself (leaves, the sums above them, pmax), insert and set, the descent, and the importance weights.  The
+floating point of the library (x^e, the quantiser, beta, the raw weight) is NOT restated here: the GPU tests take it from the
+library's host entries, which tests/test_prio_cpu.py checks against the float64 formulas below."""
+import numpy as np
+
+from tests import _placement as P_
+
+FAN = 64
+ONE = 1 << 20
+QMAX = (1 << 31) - 1
+STREAM = 7
+
+
+def worlds(N, seg, p):
+    """w_p: the worlds of network p"""
+    return max(0, min(seg, N - p * seg))
+
+
+def layout(capacity, N, seg, P):
+    """aquaprio_layout restated -> dict(levels, bytes, leaves, n, stride, offset)"""
+    L0 = capacity // N * seg
+    n, off, ns, strides, offs = L0, 0, [], [], []
+    while True:
+        stride = -(-n // FAN) * FAN
+        ns.append(n)
+        strides.append(stride)
+        offs.append(off)
+        off += P * stride * (4 if len(ns) == 1 else 8)
+        off = -(-off // 512) * 512
+        if len(ns) > 1 and n == 1:
+            break
+        n = -(-n // FAN)
+    return dict(levels=len(ns), bytes=off, leaves=L0, n=ns, stride=strides, offset=offs)
+
+
+def sums_above(leaves, n):
+    """the levels above one network's leaves, exactly: [uint64 [n_1], ..., uint64 [1]] (n: the layout's level sizes)"""
+    out, below = [], np.asarray(leaves, dtype=np.uint64)
+    for size in n[1:]:
+        padded = np.zeros(size * FAN, dtype=np.uint64)
+        padded[:below.size] = below
+        below = padded.reshape(size, FAN).sum(axis=1, dtype=np.uint64)
+        out.append(below)
+    return out
+
+
+def leaf_of_slot(slot, N, seg):
+    """-> (p, c): the network and the leaf of a slot"""
+    world, rnd = slot % N, slot // N
+    p = world // seg
+    return p, rnd * worlds(N, seg, p) + world - p * seg
+
+
+def slot_of_leaf(p, c, N, seg):
+    w = worlds(N, seg, p)
+    return (c // w) * N + p * seg + c % w
+
+
+class Trees(object):
+    """the leaves and pmax of P networks; the sums are derived when asked for"""
+
+    def __init__(self, capacity, N, seg, P):
+        self.capacity, self.N, self.seg, self.P = capacity, N, seg, P
+        self.lay = layout(capacity, N, seg, P)
+        self.leaves = np.zeros((P, self.lay["leaves"]), dtype=np.uint32)
+        self.pmax = np.full(P, ONE, dtype=np.uint32)
+
+    def insert(self, base, ok):
+        """the batch of N slots from `base` (a multiple of N inside the ring; anything else: nothing)"""
+        if base < 0 or base >= self.capacity or base % self.N != 0:
+            return
+        for i in range(self.N):
+            p, c = leaf_of_slot(base + i, self.N, self.seg)
+            if p < self.P:
+                self.leaves[p, c] = self.pmax[p] if ok[base + i] != 0 else 0
+
+    def set(self, idx, td, quantise):
+        """idx int [P][B], td float32 [P][B]; quantise(td) -> the leaf (the library's host entry).  A slot named twice with two
+        different values is not modelled (the header leaves the winner open)."""
+        for p in range(self.P):
+            for slot, x in zip(idx[p].tolist(), td[p].tolist()):
+                if slot < 0 or slot >= self.capacity or not (x >= 0.0) or not np.isfinite(x):
+                    continue
+                owner, c = leaf_of_slot(slot, self.N, self.seg)
+                if owner != p:
+                    continue
+                q = quantise(x)
+                self.leaves[p, c] = q
+                self.pmax[p] = max(int(self.pmax[p]), q)
+
+    def levels(self):
+        """[leaves [P][n_0], uint64 [P][n_1], ...] as PrioritizedReplay.levels() returns them"""
+        above = [sums_above(self.leaves[p], self.lay["n"]) for p in range(self.P)]
+        return [self.leaves.copy()] + [np.stack([above[p][k] for p in range(self.P)]) for k in range(self.lay["levels"] - 1)]
+
+
+def descend(leaves, n, u):
+    """the descent of one network's tree for the integer u in [0, root): per level, the first child whose inclusive prefix
+    exceeds u, the prefix in front of it taken off u -> the leaf index.  Python integers: exact."""
+    levels = [np.asarray(leaves, dtype=np.uint64)] + sums_above(leaves, n)
+    node = 0
+    for k in range(len(levels) - 1, 0, -1):
+        below = levels[k - 1]
+        children = [int(x) for x in below[node * FAN:(node + 1) * FAN]]
+        run, sel = 0, None
+        for lane, v in enumerate(children):
+            if run + v > u:
+                sel = lane
+                break
+            run += v
+        assert sel is not None, "the node's sum is not above u"
+        u -= run
+        node = node * FAN + sel
+    return node
+
+
+def uniform(seed, t_new, B):
+    """the 64-bit draws of samples 0 .. B - 1 of the update t_new: Python integers"""
+    r = P_.draw(seed, np.arange(B), int(t_new), STREAM, 0)
+    return [(int(a) << 32) | int(b) for a, b in zip(r[0], r[1])]
+
+
+def draw(leaves, n, seed, t, B, p, N, seg, capacity):
+    """aquaprio_draw's descent for network p -> (idx int32 [B], q uint32 [B]); t: the updates applied so far"""
+    total = int(np.asarray(leaves, dtype=np.uint64).sum(dtype=np.uint64))
+    idx, q = np.full(B, -1, dtype=np.int32), np.zeros(B, dtype=np.uint32)
+    if total == 0 or worlds(N, seg, p) == 0:
+        return idx, q
+    cum = np.cumsum(np.asarray(leaves, dtype=np.uint64), dtype=np.uint64)
+    for j, r in enumerate(uniform(seed, t + 1, B)):
+        u = (r * total) >> 64
+        c = int(np.searchsorted(cum, np.uint64(u), side="right"))        # (test_prio_cpu.py: this IS descend())
+        slot = slot_of_leaf(p, c, N, seg)
+        assert slot < capacity and leaves[c] != 0
+        idx[j], q[j] = slot, leaves[c]
+    return idx, q
+
+
+# ------------------------------------------------------------------ the weighted update
+def weighted_gradient(theta32, theta_t32, ring, eff, weight, gamma, strategy, dtype, form="mse"):
+    """tests/_learner.py::gradient with the importance weights of the samples multiplied in: w_b multiplies the TD error's
+    derivative and its square, the means still run over the n valid samples (aqua_prio.h).  weight: [B], the entries of the
+    valid samples are used.  -> dict(g, S, loss, n, td): td [B] = |Q_a - y| of every sample, -1 for what is no sample"""
+    from tests import _learner as L
+    theta, theta_t = theta32.astype(dtype), theta_t32.astype(dtype)
+    x, a, r, x2, done = L.batch_of(ring, eff, dtype)
+    n = x.shape[0]
+    td = np.full(len(eff), -1.0, dtype=np.float64)
+    if n == 0:
+        z = np.zeros(L.PARAMS, dtype=dtype)
+        return dict(g=z, S=z, loss=dtype(0), n=0, td=td)
+    w = np.asarray(weight)[eff >= 0].astype(dtype)
+    f, _ = L.bootstrap(theta, theta_t, x, x2, strategy)
+    y = r + np.where(done, dtype(0), dtype(gamma) * f).astype(dtype)
+    h1, h2, q = L.forward(theta, x)
+    (k0, b0), (k1, b1), (k2, b2) = L.unflatten(theta)
+    qa = q[np.arange(n), a]
+    td[eff >= 0] = np.abs(qa - y)
+    if form == "reference":
+        taken = np.arange(3)[None, :] == a[:, None]
+        rest = np.where(taken, dtype(0), q).sum(axis=1, dtype=dtype)
+        delta = (dtype(3) * qa - y - rest).astype(dtype)
+        sq = ((qa[:, None] - np.where(taken, y[:, None], q)) ** 2).sum(axis=1, dtype=dtype)
+        scale, mean = dtype(2.0 / (3 * n)), dtype(1.0 / (3 * n))
+    else:
+        delta = (qa - y).astype(dtype)
+        sq = delta * delta
+        scale, mean = dtype(2.0 / n), dtype(1.0 / n)
+    delta, sq = (w * delta).astype(dtype), (w * sq).astype(dtype)
+    dq = np.zeros((n, 3), dtype=dtype)
+    dq[np.arange(n), a] = delta
+    dh2 = (dq @ k2.T) * (h2 > 0)
+    dh1 = (dh2 @ k1.T) * (h1 > 0)
+    S = L.flatten([(x.T @ dh1, dh1.sum(axis=0)), (np.maximum(h1, 0).T @ dh2, dh2.sum(axis=0)), (np.maximum(h2, 0).T @ dq, dq.sum(axis=0))])
+    return dict(g=S * scale, S=S, loss=sq.sum(dtype=dtype) * mean, n=n, td=td)
+
+
+# ------------------------------------------------------------------ the float64 formulas the host entries are checked against
+def pi64(td, alpha, eps):
+    return (np.float64(td) + np.float64(eps)) ** np.float64(alpha)
+
+
+def beta64(t, beta0, anneal):
+    f = np.float64(min(int(t), int(anneal))) / np.float64(anneal)
+    b = np.float64(beta0) + (np.float64(1.0) - np.float64(beta0)) * f
+    return float(min(b, np.float64(1.0)))
+
+
+def weight64(size, q, T, beta):
+    return float((np.float64(size) * np.float64(q) / np.float64(T)) ** np.float64(-beta))
+
+
+def weights(q, T, size, beta, raw):
+    """float32 [B] from the drawn q: raw(size, q, T, beta) is the library's host entry; 0 where q == 0"""
+    w = np.array([raw(size, int(x), T, beta) if x else 0.0 for x in q], dtype=np.float64)
+    out = np.zeros(len(q), dtype=np.float32)
+    if w.max() > 0:
+        out = (w / w.max()).astype(np.float32)
+    return out
