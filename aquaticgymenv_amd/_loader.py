@@ -1,4 +1,4 @@
-"""What the fourteen ctypes bindings share: where a library lies, how it is opened and checked, and how a return code
+"""What the fifteen ctypes bindings share: where a library lies, how it is opened and checked, and how a return code
 becomes an exception.  No fallback anywhere: a missing or stale library is an ImportError."""
 import ctypes
 import os

@@ -125,10 +125,18 @@ PRIORITY_LIBRARIES = {
 }
 
 
+# Libraries behind those (the eleven tables above and what fourteen_libraries() returns are pinned as well).
+# her: hindsight experience replay, the goals of a minibatch draw relabelled from the ring with the reward recomputed
+# (csrc/aqua_her.h, beside its source for the same reason).
+HINDSIGHT_LIBRARIES = {
+    "her": _source_library("her", ["aqua_device.hpp", "aqua_host.hpp"]),
+}
+
+
 def library(name):
-    """the table entry of library `name`, from any of the eleven tables"""
+    """the table entry of library `name`, from any of the twelve tables"""
     for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
-                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES):
+                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES, HINDSIGHT_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -180,8 +188,13 @@ def thirteen_libraries():
 
 
 def fourteen_libraries():
-    """all fourteen libraries' names, the one of PRIORITY_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    """all fourteen libraries' names, the one of PRIORITY_LIBRARIES included, in build order"""
     return thirteen_libraries() + list(PRIORITY_LIBRARIES)
+
+
+def fifteen_libraries():
+    """all fifteen libraries' names, the one of HINDSIGHT_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return fourteen_libraries() + list(HINDSIGHT_LIBRARIES)
 
 
 def hipcc_path():
@@ -246,6 +259,8 @@ NSTEP_SRC, NSTEP_DEPS, NSTEP_LIB, NSTEP_FLAGS = (NSTEP_LIBRARIES["nstep"][k] for
 build_nstep, nstep_needs_build = functools.partial(build_library, "nstep"), functools.partial(needs_build, "nstep")
 PRIO_SRC, PRIO_DEPS, PRIO_LIB, PRIO_FLAGS = (PRIORITY_LIBRARIES["prio"][k] for k in ("src", "deps", "lib", "flags"))
 build_prio, prio_needs_build = functools.partial(build_library, "prio"), functools.partial(needs_build, "prio")
+HER_SRC, HER_DEPS, HER_LIB, HER_FLAGS = (HINDSIGHT_LIBRARIES["her"][k] for k in ("src", "deps", "lib", "flags"))
+build_her, her_needs_build = functools.partial(build_library, "her"), functools.partial(needs_build, "her")
 
 
 def build_variant(name, flags, verbose=False):
@@ -295,5 +310,6 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
-    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES) + list(PRIORITY_LIBRARIES):
+    for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES) + list(PRIORITY_LIBRARIES) \
+            + list(HINDSIGHT_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))

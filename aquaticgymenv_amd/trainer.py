@@ -17,7 +17,9 @@ host work between them.  With actor=, a FastActor (fastpolicy.py) over the actin
 refresh() follows stage 8: twelve kernels.  Both give, bit for bit, what examples/dqn_train.py --eager computes with ReplayRing and
 learner.update(ring, B).  With n_step > 1, an NStepReturns (nstep.py) folds the draw between stages 7 and 8 -- one kernel more in
 either variant, twelve or thirteen -- and the update learns the n-step target from its staged rows with the discount
-gamma^n; n_step = 1 is the chain above, node for node.  There is no CPU path.
+gamma^n; n_step = 1 is the chain above, node for node.  With hindsight=, a HindsightReplay (hindsight.py) relabels the draw
+between stages 7 and 8 -- one kernel more -- and the update learns from its staged rows; hindsight=None is the chain above,
+node for node.  There is no CPU path.
 """
 import ctypes
 
@@ -26,13 +28,16 @@ from .batched import RolloutGraph
 
 
 class DQNLoop(object):
-    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64, actor=None, n_step=1):
+    def __init__(self, env, qnet, learner, ring, tracker, batch_size=64, actor=None, n_step=1, hindsight=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; qnet: the acting QNetwork; learner: the DQNLearner
         that trains it; ring: a DeviceReplayRing of env; tracker: an EpisodeTracker of env with an epsilon schedule;
         actor: None, or a FastActor (fastpolicy.py) over qnet -- the act stage then launches it, and one actor.refresh()
         follows the update: one kernel more, eagerly and in the graph.  n_step: 1, or the window of an n-step target
         (nstep.py): one fold launch then goes between the draw and the update, and the ring's capacity must be a multiple of
         env.num_envs.  The discount gamma^n is passed to the update by value: a graph keeps the one of its capture.
+        hindsight: None, or a HindsightReplay (hindsight.py) of `ring` for one network and this batch size: its launch goes
+        between the draw and the update.  Not together with n_step > 1 (every step of a window would need its reward
+        recomputed).
         Everything on one device; anything else is a ValueError."""
         if env.continuous:
             raise ValueError("the DQN loop (main/impl/dqn.py) is defined for discrete actions")
@@ -58,6 +63,7 @@ class DQNLoop(object):
         self.view = ring.learner_view()
         self.idx = self.torch.full((B,), -1, dtype=self.torch.int32, device=env.device)
         self.nstep = self._make_nstep(ring, n_step, B, 1)
+        self.hindsight = self._check_hindsight(hindsight, ring, B, 1)
         env.policy_action                                     # (allocated here, not inside a capture)
         learner._grow(B)
 
@@ -68,6 +74,25 @@ class DQNLoop(object):
             return None
         from .nstep import NStepReturns
         return NStepReturns(ring, self.n_step, B, networks=networks)
+
+    def _check_hindsight(self, hindsight, ring, B, networks, priorities=None):
+        """hindsight=: None, or a HindsightReplay of this ring, batch size and number of networks; nothing is built here"""
+        if hindsight is None:
+            return None
+        if not hasattr(hindsight, "relabel") or not hasattr(hindsight, "_warm_up"):
+            raise ValueError("hindsight= must be a HindsightReplay")
+        if self.n_step != 1:
+            raise ValueError("hindsight= together with n_step=%d: every step of a window would need its reward recomputed under "
+                             "the new goal; use one of them" % self.n_step)
+        if priorities is not None:
+            raise ValueError("hindsight= together with priorities=: the TD error of a relabelled transition is not a priority of "
+                             "the stored slot; use one of them")
+        if hindsight.ring is not ring:
+            raise ValueError("hindsight= relabels from another ring than the loop's")
+        if hindsight.batch_size != B or hindsight.networks != networks:
+            raise ValueError("hindsight= stages %d x %d samples, the loop draws %d x %d"
+                             % (hindsight.networks, hindsight.batch_size, networks, B))
+        return hindsight
 
     @staticmethod
     def _check_actor(actor, policy):
@@ -103,7 +128,11 @@ class DQNLoop(object):
         ring.after_step()
         tracker.after_step()
         ring.draw(self.batch_size, self.learner, out=self.idx)
-        if self.nstep is None:
+        if self.hindsight is not None:
+            her = self.hindsight
+            her.relabel(self.idx, self.learner)               # keyed by the learner's t, which the update below advances
+            self.learner.update(her.view, self.batch_size, idx=her.idx)
+        elif self.nstep is None:
             self.learner.update(self.view, self.batch_size, idx=self.idx)
         else:
             nstep, gamma = self.nstep, self.learner.gamma
@@ -154,6 +183,8 @@ class DQNLoop(object):
         idx.fill_(-1)
         if self.nstep is not None:
             self.nstep._warm_up(with_table=False)
+        if self.hindsight is not None:
+            self.hindsight._warm_up(with_table=False)
         loss = learner.loss.clone()
         grad = learner.grad.clone()
         learner.update(self.view, self.batch_size, idx=idx)                  # no sample: nothing but loss and grad is written
@@ -168,7 +199,7 @@ class DQNLoop(object):
 
     def capture(self):
         """-> a RolloutGraph whose launch() replays one iteration: the nine stages as ONE chain of eleven kernel nodes (no
-        parallel branches; one node more with an actor, one more with n_step > 1).  It reads and advances the device state only -- tick base, epsilon, ring header, Adam's t -- so
+        parallel branches; one node more with an actor, one more with n_step > 1 or with hindsight=).  It reads and advances the device state only -- tick base, epsilon, ring header, Adam's t -- so
         every replay acts, explores, appends, draws and learns afresh; qnet.load() or learner.load_state_dict() between
         replays takes effect on the next one.  The learner's workspace is grown and every kernel has run before the capture."""
         torch, env, lib = self.torch, self.env, _capi.lib
@@ -242,10 +273,15 @@ class PopulationLoop(DQNLoop):
     follows stage 4, its draw() (two launches) is stage 6, its update() (two launches) is stage 7 and its set() follows it --
     three kernels more in every variant above.  With n_step > 1 the fold takes the draw's slots, the update the staged rows, and
     set() the draw's slots again; a window the fold dropped keeps its priority.  priorities=None is the chain above, node for
-    node.  There is no CPU path."""
+    node.
+
+    With hindsight=, a HindsightReplay (hindsight.py) of this ring for the bank's networks, its launch relabels the draw between
+    stages 6 and 7, keyed by the learners' device counters and keys, and the bank update reads its staged rows: one kernel
+    more.  Not together with n_step > 1 or priorities=.  hindsight=None is the chain above, node for node.  There is no CPU
+    path."""
 
     def __init__(self, env, bank, learners, ring, tracker, batch_size=64, segments=None, selector=None, actor=None, n_step=1,
-                 priorities=None):
+                 priorities=None, hindsight=None):
         """env: a BatchedAqua of discrete actions with normalized_obs=True; bank: the acting QNetworkBank with its epsilon
         array set; learners: the DQNLearnerBank that trains it; ring: a DeviceReplayRing of env whose capacity is a multiple
         of env.num_envs; tracker: an EpisodeTracker of env; segments: None, or a SegmentTracker of that tracker with the
@@ -254,6 +290,8 @@ class PopulationLoop(DQNLoop):
         and one actor.refresh() follows the bank update (which follows the selector when there is one): one kernel more.
         n_step: 1, or the window of an n-step target (nstep.py): one fold launch between the draw and the update.
         priorities: None, or a PrioritizedReplay (priority.py) of `ring` and `learners`: three kernels more.
+        hindsight: None, or a HindsightReplay (hindsight.py) of `ring` for bank.networks networks and this batch size: one
+        kernel more; not together with n_step > 1 or priorities=.
         Everything on one device; anything else is a ValueError."""
         from . import _lbank_capi
         if env.continuous:
@@ -312,6 +350,7 @@ class PopulationLoop(DQNLoop):
             priorities._grow(B)
             self.idx = priorities.idx                         # the draw's own row: what set() names
         self.priorities = priorities
+        self.hindsight = self._check_hindsight(hindsight, ring, B, bank.networks, priorities)
         env.policy_action                                     # (allocated here, not inside a capture)
         learners._grow(B)
 
@@ -343,7 +382,11 @@ class PopulationLoop(DQNLoop):
         # the uniform draw and the bank's update, or the descent of the sum trees and the update with its weights
         draw = self.learners.draw(ring, self.batch_size, out=self.idx) if per is None else per.draw(self.batch_size, out=self.idx)
         update = self.learners.update if per is None else per.update
-        if self.nstep is None:
+        if self.hindsight is not None:
+            her = self.hindsight
+            her.relabel(draw, self.learners)                  # keyed by the learners' t, which the update below advances
+            update(her.view, self.batch_size, her.idx)
+        elif self.nstep is None:
             update(self.view, self.batch_size, draw)
         else:
             nstep = self.nstep
@@ -393,6 +436,8 @@ class PopulationLoop(DQNLoop):
         idx.fill_(-1)
         if self.nstep is not None:
             self.nstep._warm_up(with_table=True)
+        if self.hindsight is not None:
+            self.hindsight._warm_up(with_table=True)
         if self.priorities is not None:
             self.priorities._warm_up(self.view)                              # scratch trees; its update, without a sample
         else:

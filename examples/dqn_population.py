@@ -32,9 +32,14 @@ over its slots of the ring, importance weights in the update, the new TD errors 
 inside the graph.  --per-alpha, --per-beta0 and --per-anneal are the exponent of the priorities, the first importance exponent
 and the updates over which it rises to 1.
 
+--her relabels the goals of every network's drawn transitions in hindsight (hindsight.HindsightReplay, libaqua_her.so): one
+more kernel replays a share --her-ratio of them under a goal their own world reached within the next --her-horizon steps,
+keyed by the learners' device counters and keys.  Not together with --n-step or --per.
+
     python examples/dqn_population.py [--networks 8] [--seg 256] [--steps 3000] [--batch 64] [--obstacles] [--host-refresh]
                                       [--pbt] [--pbt-ready 100] [--pbt-fraction 0.25] [--pbt-every 1] [--fast] [--n-step 3]
                                       [--per] [--per-alpha 0.6] [--per-beta0 0.4] [--per-anneal 100000]
+                                      [--her] [--her-ratio 0.8] [--her-horizon 32]
 """
 import argparse
 import os
@@ -73,7 +78,12 @@ ap.add_argument("--per", action="store_true", help="prioritised experience repla
 ap.add_argument("--per-alpha", type=float, default=0.6, help="with --per: the exponent of the priorities (0: uniform)")
 ap.add_argument("--per-beta0", type=float, default=0.4, help="with --per: the importance exponent of the first update")
 ap.add_argument("--per-anneal", type=int, default=100000, help="with --per: updates over which the importance exponent rises to 1")
+ap.add_argument("--her", action="store_true", help="hindsight experience replay on the device (HindsightReplay)")
+ap.add_argument("--her-ratio", type=float, default=0.8, help="with --her: the share of the eligible samples that is relabelled")
+ap.add_argument("--her-horizon", type=int, default=32, help="with --her: how many steps ahead a goal may lie")
 args = ap.parse_args()
+if args.her and (args.per or args.n_step != 1):
+    ap.error("--her relabels one stored step under a uniform draw: it does not go with --n-step or --per")
 if args.pbt and args.host_refresh:
     ap.error("--pbt judges the networks by the SegmentTracker's statistics: it does not go with --host-refresh")
 
@@ -119,8 +129,12 @@ priorities = None
 if args.per:
     from aquaticgymenv_amd.priority import PrioritizedReplay
     priorities = PrioritizedReplay(ring, learners, alpha=args.per_alpha, beta0=args.per_beta0, anneal=args.per_anneal)
+hindsight = None
+if args.her:
+    from aquaticgymenv_amd.hindsight import HindsightReplay
+    hindsight = HindsightReplay(ring, args.batch, networks=P, horizon=args.her_horizon, ratio=args.her_ratio)
 graph = PopulationLoop(env, bank, learners, ring, tracker, args.batch, segments=segments, selector=selector, actor=actor, n_step=args.n_step,
-                       priorities=priorities).capture()
+                       priorities=priorities, hindsight=hindsight).capture()
 decay = (EPS_FINAL / EPS_INIT) ** (1.0 / args.epsilon_decay)  # dqn.py:139-140
 episodes, seen = np.zeros(P, dtype=np.int64), 0               # --host-refresh: finished episodes per network, and in all
 for step in range(1, args.steps + 1):

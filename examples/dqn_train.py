@@ -20,7 +20,12 @@ split copy of the weights is refreshed after every update, inside the graph: one
 --n-step K learns the K-step target: one more kernel in the graph folds the K transitions that follow every drawn one into a
 staged minibatch (nstep.NStepReturns), and the update bootstraps with gamma^K.  The ring then holds whole batched steps.
 
+--her relabels the goals of the drawn transitions in hindsight (hindsight.HindsightReplay, libaqua_her.so): one more kernel in
+the graph replays a share --her-ratio of them under a goal their own world reached within the next --her-horizon steps, with
+the reward recomputed exactly.  The ring then holds whole batched steps.  Not together with --n-step or --eager.
+
     python examples/dqn_train.py [--envs 1024] [--steps 3000] [--batch 256] [--obstacles] [--eager] [--fast] [--n-step 3]
+                                 [--her] [--her-ratio 0.8] [--her-horizon 32]
 """
 import argparse
 import os
@@ -50,9 +55,14 @@ ap.add_argument("--loss", choices=("mse", "reference"), default="mse",
 ap.add_argument("--eager", action="store_true", help="issue every launch of the iteration from Python (ReplayRing) instead of replaying one graph")
 ap.add_argument("--fast", action="store_true", help="act on the f16 MFMA, operands split hi / lo (FastActor, refreshed after every update)")
 ap.add_argument("--n-step", type=int, default=1, help="the window of the multi-step target (1: the reference's one-step target)")
+ap.add_argument("--her", action="store_true", help="hindsight experience replay on the device (HindsightReplay)")
+ap.add_argument("--her-ratio", type=float, default=0.8, help="with --her: the share of the eligible samples that is relabelled")
+ap.add_argument("--her-horizon", type=int, default=32, help="with --her: how many steps ahead a goal may lie")
 args = ap.parse_args()
 if args.n_step != 1 and args.eager:
     ap.error("--n-step folds the device ring: it goes with the graph, not with --eager")
+if args.her and (args.eager or args.n_step != 1):
+    ap.error("--her relabels from the device ring, one step at a time: it goes with the graph, and not with --n-step")
 
 # default_hyperparam of dqn.py
 EPS_INIT, EPS_FINAL, GAMMA, TAU = 1.0, 0.05, 0.98, 0.005
@@ -68,7 +78,7 @@ learner = DQNLearner(qnet, gamma=GAMMA, tau=TAU, lr=1e-3, strategy="double_ref",
 env = BatchedAqua(args.envs, obstacles=args.obstacles, seed=args.seed, auto_reset="next_step", normalized_obs=True)
 env.reset()
 capacity = max(args.buffer, args.envs)
-if args.n_step != 1:
+if args.n_step != 1 or args.her:
     capacity -= capacity % args.envs                           # whole batched steps: a world's next step is one batch further
 ring = (ReplayRing if args.eager else DeviceReplayRing)(env, capacity=capacity)
 tracker = EpisodeTracker(env, epsilon=(EPS_INIT, EPS_FINAL, args.epsilon_decay))     # decay >= 1: episodes to reach EPS_FINAL
@@ -76,7 +86,12 @@ actor = None
 if args.fast:
     from aquaticgymenv_amd.fastpolicy import FastActor
     actor = FastActor(qnet)
-graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch, actor=actor, n_step=args.n_step).capture()
+hindsight = None
+if args.her:
+    from aquaticgymenv_amd.hindsight import HindsightReplay
+    hindsight = HindsightReplay(ring, args.batch, horizon=args.her_horizon, ratio=args.her_ratio)
+graph = None if args.eager else DQNLoop(env, qnet, learner, ring, tracker, args.batch, actor=actor, n_step=args.n_step,
+                                        hindsight=hindsight).capture()
 for step in range(1, args.steps + 1):
     if graph is not None:
         graph.launch()                                         # the nine stages below and the tick advance, as one graph
