@@ -198,3 +198,27 @@ def weights(q, T, size, beta, raw):
     if w.max() > 0:
         out = (w / w.max()).astype(np.float32)
     return out
+
+
+# ------------------------------------------------------------------ inputs on a tie of the quantiser, found through the host entries
+def tie_eps(capi, k):
+    """eps (td = 0, alpha = 1) whose scaled priority is EXACTLY k + 1/2 by the library's own x^e, next to (k + 1/2) 2^-20, or
+    None: ln x moves in steps of its own last place, so only some k have one"""
+    at = np.float64((k + 0.5) / ONE)
+    for step in range(-40, 41):
+        eps = float(at + step * np.spacing(at))
+        if capi.pow_(eps, 1.0) * ONE == k + 0.5:
+            return eps
+    return None
+
+
+def ties(capi):
+    """[(k, eps)]: the first two odd and the first two even k below 120 that have a tie"""
+    out = {0: [], 1: []}
+    for k in range(1, 120):
+        if len(out[k & 1]) < 2:
+            eps = tie_eps(capi, k)
+            if eps is not None:
+                out[k & 1].append((k, eps))
+    assert len(out[0]) == 2 and len(out[1]) == 2, "no tie found for both parities"
+    return out[0] + out[1]

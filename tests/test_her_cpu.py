@@ -230,6 +230,8 @@ def test_threshold_is_the_floor_of_ratio_times_two_to_the_32(capi):
                         (2.0 ** -32, 1)):
         assert capi.threshold(ratio) == want == M.threshold(ratio), ratio
     assert 3435973836 == (8 * 2 ** 32) // 10                       # 0.8 as a double lies above 4/5 by less than 2^-32
+    for word in (1, 12345, 2 ** 31, 2 ** 32 - 2):                  # half a unit above a word: the floor, not the ceiling or the nearest
+        assert capi.threshold((word + 0.5) / 2.0 ** 32) == word == M.threshold((word + 0.5) / 2.0 ** 32)
     for bad in (-1e-300, 1.0 + 2.0 ** -52, float("nan"), float("inf"), -float("inf"), 2.0, -0.5):
         out = ctypes.c_uint64(77)
         assert capi.lib.aquaher_threshold(bad, ctypes.byref(out)) == capi.E_INVALID and "ratio" in capi.last_error() and out.value == 77

@@ -314,6 +314,16 @@ def test_quantiser_equals_the_float64_model_away_from_ties(capi):
             capi.quantise(td, alpha, eps)
 
 
+def test_quantiser_rounds_ties_to_even(capi):
+    """the values the test above leaves out: eps (td = 0, alpha = 1) whose scaled priority is exactly k + 1/2 by the library's
+    own x^e (tests/_prio_model.py::ties finds two odd and two even k) quantises to the even neighbour"""
+    ties = M.ties(capi)
+    assert sorted(k & 1 for k, _ in ties) == [0, 0, 1, 1]
+    for k, eps in ties:
+        assert capi.pow_(eps, 1.0) * M.ONE == k + 0.5 and abs(eps * M.ONE - (k + 0.5)) <= (k + 0.5) * 2.0 ** -44
+        assert capi.quantise(0.0, 1.0, eps) == k + (k & 1), (k, eps)
+
+
 def test_beta_is_the_formula_bit_for_bit_and_the_weights_are_close(capi):
     for beta0 in (0.0, 0.4, 0.7, 1.0):
         for anneal in (1, 3, 1000, 100000, 2 ** 40):

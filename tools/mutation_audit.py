@@ -1,5 +1,7 @@
 #!/usr/bin/env python
-"""Mutation audit of the DQN libraries (policy, bank, episodes, replay, learner): does the GPU suite bite?
+"""Mutation audit of thirteen device libraries: does the GPU suite bite?
+
+First audit: policy, bank, episodes, replay, learner.  Second audit: lbank, segments, pbt, qmap, fastpol, nstep, prio, her.
 
 A mutant is a patch tools/mutants/<library>/<name>.patch: a one-line description, then a small unified diff against ONE
 file under aquaticgymenv_amd/csrc/.  Mutant libraries and the scratch trees they are built in are never committed.
@@ -7,7 +9,8 @@ file under aquaticgymenv_amd/csrc/.  Mutant libraries and the scratch trees they
 THE RULE FOR MUTANTS (enforced by review).  Each mutant changes the VALUE of one arithmetic expression, constant or value
 comparison.  None changes an index, an address, a bound on an index, a loop trip count, a barrier or fence, an LDS layout,
 a launch shape or an argument check.  A mutant must be unable to read or write where the shipped kernel does not: the aim
-is a failing assertion, never a fault.
+is a failing assertion, never a fault.  A value that later selects a slot (the k of a relabelling draw, a window limit) is
+mutated only where the mutated arithmetic itself still proves the range, and the patch's description line says why.
 
   --build [LIB[/NAME] ...]   for every patch: copy csrc/, include/ and build.py into a scratch tree of its own (never the
                              working tree), apply the patch there (one that no longer applies is an error and the exit
@@ -15,13 +18,15 @@ is a failing assertion, never a fault.
                              each_library(), cross-compiled for gfx950, no GPU needed) and put the result at
                              gpu_jobs/mutants/<library>/<name>.so (a folder that travels to the GPU machine and stays
                              out of git).
-  --run LIB/NAME             one pytest child over the GPU test files of that library (FILES below) with the mutant
+  --run LIB/NAME             one pytest child over the GPU test files of that library (FILES below) and, of the file
+                             its audit added, the cases named for that library (selection_of) with the mutant
                              substituted through the variable the binding's lib_path() honours; writes
                              <out>/<library>/<name>.json, .xml and .log.  Exit status 0: survived, 1: killed; anything
                              else (a crash of the child, a HIP error text in its log) is passed on as a status >= 2 and
                              the caller must stop: read what it left before anything else runs on the GPU.  No retries.
   --list                     LIB/NAME of every patch, one per line (what a job script loops over)
-  --collect                  <out>/**.json -> profiles/mutation_audit.json and the tables for profiles/LOG.md on stdout
+  --collect                  <out>/**.json -> profiles/mutation_audit.json and the tables for profiles/LOG.md on stdout.
+                             It MERGES: a mutant without a run under <out> keeps the record it has, bit for bit
   --out DIR                  where --run writes and --collect reads (default build/mutation, which git ignores): a job on
                              another machine names a folder whose contents come back from it
 
@@ -47,7 +52,8 @@ OUT_LIBS = os.path.join(ROOT, "gpu_jobs", "mutants")
 OUT_RUNS = os.path.join(ROOT, "build", "mutation")          # --out replaces it
 RECORD = os.path.join(ROOT, "profiles", "mutation_audit.json")
 
-LIBRARIES = ("policy", "bank", "episodes", "replay", "learner")
+LIBRARIES = ("policy", "bank", "episodes", "replay", "learner",                    # the first audit
+             "lbank", "segments", "pbt", "qmap", "fastpol", "nstep", "prio", "her")   # the second
 ENV = {lib: "AQUA_%s_LIB" % lib.upper() for lib in LIBRARIES}              # what _<lib>_capi.py hands to _loader.lib_path()
 TRAINER = "tests/test_trainer_gpu.py"
 FILES = {                                                                  # the GPU test files of a library, before the audit
@@ -56,9 +62,34 @@ FILES = {                                                                  # the
     "episodes": ["tests/test_episodes_gpu.py", TRAINER],
     "replay": ["tests/test_replay_gpu.py", TRAINER],
     "learner": ["tests/test_learner_gpu.py", "tests/test_learner_forms_gpu.py", TRAINER],
+    # the second audit: each of these files also holds the loop tests (DQNLoop / PopulationLoop) that run its library
+    "lbank": ["tests/test_lbank_gpu.py"],
+    "segments": ["tests/test_segments_gpu.py"],
+    "pbt": ["tests/test_pbt_gpu.py"],
+    "qmap": ["tests/test_qmaps_gpu.py"],
+    "fastpol": ["tests/test_fastpol_gpu.py"],
+    "nstep": ["tests/test_nstep_gpu.py"],
+    "prio": ["tests/test_prio_gpu.py"],
+    "her": ["tests/test_her_gpu.py"],
 }
-NEW_FILES = ["tests/test_dqn_knife_gpu.py", "tests/test_dqn_poison_gpu.py"]   # what the audit added: the "after" column
+# what the audits added: the "after" column
+NEW_FILES = ["tests/test_dqn_knife_gpu.py", "tests/test_dqn_poison_gpu.py", "tests/test_population_knife_gpu.py"]
+FIRST_AUDIT = LIBRARIES[:5]
+NEW_FILES_OF = {lib: (NEW_FILES[:2] if lib in FIRST_AUDIT else NEW_FILES[2:]) for lib in LIBRARIES}   # an audit's own new files
 HIP_ERROR = re.compile(r"HIP error|hipError|illegal memory access|Memory access fault|HSA_STATUS_ERROR", re.I)
+
+
+def files_of(lib):
+    """the test files one --run of a mutant of `lib` goes over: the library's own, then what its audit added (if it exists yet)"""
+    return FILES[lib] + [f for f in NEW_FILES_OF[lib] if os.path.exists(os.path.join(ROOT, f))]
+
+
+def selection_of(lib):
+    """pytest arguments that keep, of the second audit's knife file, the cases of `lib` alone (they are named
+    test_<lib>_...; the other libraries are the shipped ones in this run, their cases could only pass): [] for the first audit"""
+    if lib in FIRST_AUDIT:
+        return []
+    return ["-k", "not (%s)" % " or ".join("test_%s_" % other for other in LIBRARIES if other not in FIRST_AUDIT and other != lib)]
 
 
 def patches(selection=()):
@@ -92,6 +123,8 @@ def build_one(lib, name, path):
         os.makedirs(pkg)
         shutil.copytree(os.path.join(ROOT, "aquaticgymenv_amd", "csrc"), os.path.join(pkg, "csrc"))
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(scratch, "include"))
+        if os.path.isdir(os.path.join(ROOT, "aquaticgymenv_amd", "include")):      # the headers of the package's own libraries
+            shutil.copytree(os.path.join(ROOT, "aquaticgymenv_amd", "include"), os.path.join(pkg, "include"))
         shutil.copy(os.path.join(ROOT, "aquaticgymenv_amd", "build.py"), pkg)
         # git apply outside a repository is a strict `patch`: no fuzz, and text in front of the diff is skipped
         r = subprocess.run(["git", "apply", "--verbose", path], cwd=scratch, capture_output=True, text=True)
@@ -100,7 +133,9 @@ def build_one(lib, name, path):
         spec = importlib.util.spec_from_file_location("aqua_mutant_build_%s_%s" % (lib, name), os.path.join(pkg, "build.py"))
         build = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(build)
-        if lib not in build.each_library():
+        try:                                                        # (each_library() ends at the bank: library() looks in every table)
+            build.library(lib)
+        except KeyError:
             return what, "build.py knows no library %r" % lib
         try:
             built = build.build_library(lib, force=True)
@@ -138,10 +173,10 @@ def cmd_run(what):
     out_dir = os.path.join(OUT_RUNS, lib)
     os.makedirs(out_dir, exist_ok=True)
     xml, log = os.path.join(out_dir, name + ".xml"), os.path.join(out_dir, name + ".log")
-    files = FILES[lib] + [f for f in NEW_FILES if os.path.exists(os.path.join(ROOT, f))]
+    files = files_of(lib)
     env = dict(os.environ)
     env[ENV[lib]] = so
-    cmd = [sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", "--tb=line", "--junitxml", xml] + files
+    cmd = [sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", "--tb=line", "--junitxml", xml] + selection_of(lib) + files
     with open(log, "w") as f:
         rc = subprocess.run(cmd, cwd=ROOT, env=env, stdout=f, stderr=subprocess.STDOUT).returncode
     with open(log) as f:
@@ -166,11 +201,17 @@ def cmd_run(what):
 
 
 def cmd_collect():
-    record, missing = {"files": FILES, "new_files": NEW_FILES, "mutants": []}, []
+    record, missing, kept = {"files": FILES, "new_files": NEW_FILES, "mutants": []}, [], {}
+    if os.path.exists(RECORD):                                      # merge: what is not re-run keeps its record
+        with open(RECORD) as f:
+            kept = {(m["library"], m["mutant"]): m for m in json.load(f)["mutants"]}
     for lib, name, path, desc in patches():
         run = os.path.join(OUT_RUNS, lib, name + ".json")
         if not os.path.exists(run):
-            missing.append("%s/%s" % (lib, name))
+            if (lib, name) in kept:
+                record["mutants"].append(kept[(lib, name)])
+            else:
+                missing.append("%s/%s" % (lib, name))
             continue
         with open(run) as f:
             r = json.load(f)
