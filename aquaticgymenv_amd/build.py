@@ -133,10 +133,18 @@ HINDSIGHT_LIBRARIES = {
 }
 
 
+# Libraries behind those (the twelve tables above and what fifteen_libraries() returns are pinned as well).
+# ens: the ensemble policy, every member network of a bank on every world of a batch reduced to one action per world
+# (csrc/aqua_ens.h, beside its source for the same reason).
+ENSEMBLE_LIBRARIES = {
+    "ens": _source_library("ens", ["aqua_device.hpp", "aqua_host.hpp", "aqua_qnet.hpp"]),
+}
+
+
 def library(name):
     """the table entry of library `name`, from any of the twelve tables"""
     for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
-                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES, HINDSIGHT_LIBRARIES):
+                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES, HINDSIGHT_LIBRARIES, ENSEMBLE_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -195,6 +203,11 @@ def fourteen_libraries():
 def fifteen_libraries():
     """all fifteen libraries' names, the one of HINDSIGHT_LIBRARIES included, in build order (what build() and `python -m` compile)"""
     return fourteen_libraries() + list(HINDSIGHT_LIBRARIES)
+
+
+def sixteen_libraries():
+    """all sixteen libraries' names, the one of ENSEMBLE_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return fifteen_libraries() + list(ENSEMBLE_LIBRARIES)
 
 
 def hipcc_path():
@@ -261,6 +274,8 @@ PRIO_SRC, PRIO_DEPS, PRIO_LIB, PRIO_FLAGS = (PRIORITY_LIBRARIES["prio"][k] for k
 build_prio, prio_needs_build = functools.partial(build_library, "prio"), functools.partial(needs_build, "prio")
 HER_SRC, HER_DEPS, HER_LIB, HER_FLAGS = (HINDSIGHT_LIBRARIES["her"][k] for k in ("src", "deps", "lib", "flags"))
 build_her, her_needs_build = functools.partial(build_library, "her"), functools.partial(needs_build, "her")
+ENS_SRC, ENS_DEPS, ENS_LIB, ENS_FLAGS = (ENSEMBLE_LIBRARIES["ens"][k] for k in ("src", "deps", "lib", "flags"))
+build_ens, ens_needs_build = functools.partial(build_library, "ens"), functools.partial(needs_build, "ens")
 
 
 def build_variant(name, flags, verbose=False):
@@ -311,5 +326,5 @@ if __name__ == "__main__":
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
     for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES) + list(PRIORITY_LIBRARIES) \
-            + list(HINDSIGHT_LIBRARIES):
+            + list(HINDSIGHT_LIBRARIES) + list(ENSEMBLE_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))
