@@ -141,10 +141,18 @@ ENSEMBLE_LIBRARIES = {
 }
 
 
+# Libraries behind those (the thirteen tables above and what sixteen_libraries() returns are pinned as well).
+# evo: natural evolution strategies on a bank, antithetic perturbations of one centre, mid-rank fitness shaping and the
+# centre's optimiser step (csrc/aqua_evo.h, beside its source for the same reason).
+EVOLUTION_LIBRARIES = {
+    "evo": _source_library("evo", ["aqua_host.hpp"]),
+}
+
+
 def library(name):
     """the table entry of library `name`, from any of the twelve tables"""
     for table in (LIBRARIES, EXTRA_LIBRARIES, BANK_LIBRARIES, POPULATION_LIBRARIES, SEGMENT_LIBRARIES, SELECTION_LIBRARIES, MAP_LIBRARIES,
-                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES, HINDSIGHT_LIBRARIES, ENSEMBLE_LIBRARIES):
+                  FAST_LIBRARIES, NSTEP_LIBRARIES, PRIORITY_LIBRARIES, HINDSIGHT_LIBRARIES, ENSEMBLE_LIBRARIES, EVOLUTION_LIBRARIES):
         if name in table:
             return table[name]
     return ADDON_LIBRARIES[name]
@@ -208,6 +216,11 @@ def fifteen_libraries():
 def sixteen_libraries():
     """all sixteen libraries' names, the one of ENSEMBLE_LIBRARIES included, in build order (what build() and `python -m` compile)"""
     return fifteen_libraries() + list(ENSEMBLE_LIBRARIES)
+
+
+def seventeen_libraries():
+    """all seventeen libraries' names, the one of EVOLUTION_LIBRARIES included, in build order (what build() and `python -m` compile)"""
+    return sixteen_libraries() + list(EVOLUTION_LIBRARIES)
 
 
 def hipcc_path():
@@ -276,6 +289,8 @@ HER_SRC, HER_DEPS, HER_LIB, HER_FLAGS = (HINDSIGHT_LIBRARIES["her"][k] for k in 
 build_her, her_needs_build = functools.partial(build_library, "her"), functools.partial(needs_build, "her")
 ENS_SRC, ENS_DEPS, ENS_LIB, ENS_FLAGS = (ENSEMBLE_LIBRARIES["ens"][k] for k in ("src", "deps", "lib", "flags"))
 build_ens, ens_needs_build = functools.partial(build_library, "ens"), functools.partial(needs_build, "ens")
+EVO_SRC, EVO_DEPS, EVO_LIB, EVO_FLAGS = (EVOLUTION_LIBRARIES["evo"][k] for k in ("src", "deps", "lib", "flags"))
+build_evo, evo_needs_build = functools.partial(build_library, "evo"), functools.partial(needs_build, "evo")
 
 
 def build_variant(name, flags, verbose=False):
@@ -326,5 +341,5 @@ if __name__ == "__main__":
         for name, flags in (("stamps", ["-DAQUA_STAMPS=1"]), ("nw", ["-DAQUA_NS_NOWORK"]), ("nm", ["-DAQUA_NS_NOMAIN"])):
             print(build_variant(name, flags, verbose=True))
     for name in nine_libraries() + list(SELECTION_LIBRARIES) + list(MAP_LIBRARIES) + list(FAST_LIBRARIES) + list(NSTEP_LIBRARIES) + list(PRIORITY_LIBRARIES) \
-            + list(HINDSIGHT_LIBRARIES) + list(ENSEMBLE_LIBRARIES):
+            + list(HINDSIGHT_LIBRARIES) + list(ENSEMBLE_LIBRARIES) + list(EVOLUTION_LIBRARIES):
         print(build_library(name, force="--force" in sys.argv, verbose=True))
